@@ -17,6 +17,8 @@ PyTorch baseline of the reference algorithm measured on the same MI355X
     python bench.py --impl reference     # the reference's eager op sequence (baseline)
     python bench.py --gpus 8             # spawns 8 rank processes itself (no torchrun needed)
     torchrun --nproc-per-node 8 bench.py --gpus 8
+    python bench.py --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --full               # + the measurements beyond the headline figure (none today)
 
 Launch contract: under torchrun (WORLD_SIZE set) every process is one rank and
 ``--gpus`` must equal WORLD_SIZE.  Without WORLD_SIZE and ``--gpus N > 1`` the
@@ -80,7 +82,38 @@ def parse():
                          "(graph 394.6 vs eager 402.0 pairs/s on MI355X; 1080p inference 60.9 graph vs 60.7 eager, profiles/r3_graph_vs_eager.log)")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: gloo-backend plumbing check of the launch path only (tests), never a measurement")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (fp32; "
+                         "train: loss, metric_*, the final flow prediction, the parameters after the step; infer: "
+                         "flow_low, flow_up).  Inputs and initial weights are seeded, so two builds run with the same "
+                         "arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure.  A plain single-GPU "
+                         "run is already only set-up, warm-up, the timed steps and the result line, so today this "
+                         "adds nothing; secondary measurements added later belong behind it")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6  # all of --dump-outputs together stays below 64 MB
+
+
+def _dump_outputs(path, tensors):
+    """Write ``{name: tensor}`` as ``path/<name>.npy`` (float32).  When the arrays together exceed
+    DUMP_BUDGET_BYTES every array above its equal share is replaced by a fixed, seeded sample of its
+    flattened elements (the same indices in every run of the same shapes)."""
+    import numpy as np
+
+    arrays = {k: v.detach().to(dtype=torch.float32, device="cpu").contiguous().numpy() for k, v in tensors.items()
+              if torch.is_tensor(v)}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // (4 * len(arrays))
+        for k, a in arrays.items():
+            if a.size > share:
+                idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share))
+                arrays[k] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _sync(device):
@@ -239,6 +272,9 @@ def run(args):
     pool = [synthetic_batch(max(args.batch, 1), H, W, seed=rank * 97 + i, device=device)
             for i in range(2 if H * W > 1e6 else 4)]
 
+    # --dump-outputs: the step's returned tensors are kept by reference (no copy, no extra kernel)
+    kept = {} if (args.dump_outputs and rank == 0) else None
+
     if args.mode == "infer":
         from raft_ros_amd.runtime import GraphedRAFT
 
@@ -248,7 +284,9 @@ def run(args):
         @torch.inference_mode()
         def step(i):
             i1, i2, flow, valid = pool[i % len(pool)]
-            _, flow_up = runner(i1, i2)
+            flow_low, flow_up = runner(i1, i2)
+            if kept is not None:
+                kept.update(flow_low=flow_low, flow_up=flow_up)
             return flow_up.new_zeros(()), {"epe": (flow_up - flow).norm(dim=1).mean()}
     else:
         step = None
@@ -264,6 +302,8 @@ def run(args):
             init_idle_scaler(scaler, device)
         else:
             preds = ddp(i1, i2, iters=args.iters)
+            if kept is not None:
+                kept["flow"] = preds[-1].detach()  # a view: keeps the tensor, not the autograd graph
             loss, metrics = sequence_loss(preds, flow, valid, gamma=0.8)
             if weight != 1.0:
                 loss = loss * weight
@@ -338,6 +378,12 @@ def run(args):
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if kept is not None:
+        kept["loss"] = loss
+        kept.update({"metric_" + k: torch.as_tensor(v) for k, v in metrics.items()})
+        if args.mode == "train":
+            kept["params"] = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+        _dump_outputs(args.dump_outputs, kept)
     ar_ms = _allreduce_ms(model, device, world)
     enc_path, upd_path = _paths(model, pool[0][0], args)
     pairs = (args.global_batch if sizes is not None else args.batch * world) * args.steps

@@ -13,7 +13,8 @@ reference forward exactly as demo.py:56-62 does: InputPadder (sintel mode, 436 -
 * ``flow_up`` (1, 2, 440, 1024) fp32 subsampled every 4th row / column (keeps the file small);
 * ``ck_<name>``: sum of squares of every parameter (weight checksum).
 
-Output: ``tests/fixtures/golden_demo_frames.npz`` (consumed by tests/test_golden_gpu.py and
+Output: ``tests/golden/golden_demo_frames_base.npz`` (RAFT base) and
+``tests/golden/golden_demo_frames_small.npz`` (RAFT small) (consumed by tests/test_golden_gpu.py and
 tests/test_golden_cpu.py).  The reference is imported read-only (no bytecode written).
 """
 from __future__ import annotations
@@ -77,9 +78,14 @@ def main():
             print(f"{name} pair {p}: {a.shape[-2:]} {time.time() - t0:.1f} s, |flow| mean {up.norm(dim=1).mean():.3f}")
             out[f"{name}/pair{p}/flow_low"] = lo.numpy().astype(np.float32)
             out[f"{name}/pair{p}/flow_up_sub"] = up[:, :, ::SUB, ::SUB].numpy().astype(np.float32).copy()
-    path = os.path.join(ROOT, "tests", "fixtures", "golden_demo_frames.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    # one file per model, each below 1 MiB (tests/golden.py fixture() merges them)
+    small = {k: v for k, v in out.items() if k.startswith("small/")}
+    base = {k: v for k, v in out.items() if k not in small}
+    for path, part in ((os.path.join(ROOT, "tests", "golden", "golden_demo_frames_base.npz"), base),
+                       (os.path.join(ROOT, "tests", "golden", "golden_demo_frames_small.npz"), small)):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        np.savez_compressed(path, **part)
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":

@@ -7,12 +7,17 @@ import torch
 from PIL import Image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = os.path.join(ROOT, "tests", "fixtures", "golden_demo_frames.npz")
+# one file per model (each below 1 MiB): RAFT base + the shared settings, RAFT small
+FIXTURES = [os.path.join(ROOT, "tests", "golden", "golden_demo_frames_base.npz"),
+            os.path.join(ROOT, "tests", "golden", "golden_demo_frames_small.npz")]
 FRAMES = ["frame_0016.png", "frame_0017.png", "frame_0018.png"]
 
 
 def fixture():
-    return np.load(FIXTURE, allow_pickle=False)
+    out = {}
+    for path in FIXTURES:
+        out.update(np.load(path, allow_pickle=False))
+    return out
 
 
 def frames():
@@ -111,3 +116,48 @@ def grad_errors(grads, fix, name):
             ref = torch.from_numpy(fix[f"{name}/gproj/{pn}"])
             errs[pn] = float((projections(pn, g.numel()) @ g - ref).norm() / ref.norm())
     return errs
+
+
+# ------------------------------------------------------------------ recorded reference outputs (CPU parity)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def parity_helpers():
+    """(parity_images, viz_flow) of scripts/make_golden_parity.py, which recorded tests/golden/."""
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    from make_golden_parity import parity_images, viz_flow
+
+    return parity_images, viz_flow
+
+
+def parity_model(small: bool, seed: int, ck):
+    """Seed-``seed`` random-init RAFT: the weights the reference ran with (checked by checksum ``ck``,
+    a mapping name -> sum of squares)."""
+    from raft_ros_amd.models import RAFT
+
+    torch.manual_seed(seed)
+    m = RAFT(Namespace(small=small, mixed_precision=False, alternate_corr=False))
+    sd = m.state_dict()
+    floats = [k for k, v in sd.items() if v.dtype.is_floating_point]
+    assert sorted(floats) == sorted(ck), set(floats) ^ set(ck)
+    for k in floats:
+        want, got = float(ck[k]), float((sd[k].double() ** 2).sum())
+        assert abs(got - want) <= 1e-9 * max(abs(want), 1.0), (k, got, want)
+    return m
+
+
+def parity_grads():
+    """-> ({param: reference gradient (fp32 tensor, flat)}, weight checksums) of raft_grads_small_*."""
+    import json
+
+    with open(os.path.join(GOLDEN, "raft_grads_small.json")) as f:
+        meta = json.load(f)
+    flat = np.concatenate([np.load(os.path.join(GOLDEN, f"raft_grads_small_{i}.npy")) for i in range(meta["chunks"])])
+    assert flat.size == sum(n for _, n in meta["params"])
+    out, off = {}, 0
+    for name, n in meta["params"]:
+        out[name] = torch.from_numpy(flat[off:off + n])
+        off += n
+    return out, meta["ck"]

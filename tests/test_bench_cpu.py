@@ -78,3 +78,21 @@ def test_bench_global_batch_strong_scaling_with_idle_rank():
     assert r["config"]["global_batch"] == 1 and r["config"]["rank_batches"] == [1, 0]
     assert r["vs_baseline"] is None
     assert abs(r["value"] - 1 * 2 / (r["ms_per_step"] * 2 / 1000.0)) / r["value"] < 1e-2
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy files (here the CPU step:
+    loss, metrics, final flow prediction, parameters after the step); --full is accepted and the
+    result line keeps its keys."""
+    import numpy as np
+
+    d = tmp_path / "dump"
+    r = _bench("--full", "--dump-outputs", str(d))
+    assert KEYS <= set(r) and r["ms_per_step"] > 0
+    got = {p.name: np.load(p) for p in d.iterdir()}
+    assert {"loss.npy", "metric_epe.npy", "flow.npy", "params.npy"} <= set(got)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["flow.npy"].shape == (1, 2, 128, 128) and got["params.npy"].shape == (990162,)
+    assert abs(float(got["loss.npy"]) - r["final_loss"]) < 1e-3
+    assert sum(a.nbytes for a in got.values()) <= 64 * 10**6

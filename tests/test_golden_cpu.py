@@ -1,5 +1,5 @@
 """Golden parity on CPU: our RAFT (module path, fp32) vs outputs of the REAL reference
-implementation stored in tests/fixtures/golden_demo_frames.npz (scripts/make_golden.py):
+implementation stored in tests/golden/golden_demo_frames_{base,small}.npz (scripts/make_golden.py):
 seed-0 weights, the reference's demo frames 0016-0018 (436x1024 padded to 440x1024),
 20 iterations, test_mode -- the demo.py / ROS configuration."""
 import pytest

@@ -1,5 +1,5 @@
 """Golden parity on the GPU against the REAL reference implementation's outputs
-(tests/fixtures/golden_demo_frames.npz, scripts/make_golden.py: reference core.raft.RAFT on
+(tests/golden/golden_demo_frames_{base,small}.npz, scripts/make_golden.py: reference core.raft.RAFT on
 the CPU in fp32, seed-0 weights, the reference's demo frames, 440x1024, 20 iterations,
 test_mode -- the demo.py / ROS node configuration).
 

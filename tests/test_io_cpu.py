@@ -1,4 +1,6 @@
 """File formats: .flo, .pfm, KITTI 16-bit PNG, the PNG codec, read_gen, the chairs split."""
+import os
+
 import numpy as np
 import pytest
 from PIL import Image
@@ -86,6 +88,6 @@ def test_chairs_split():
 
 
 @pytest.mark.reference
-def test_chairs_split_matches_reference_file(reference_core):
-    ref = np.loadtxt("/root/reference/chairs_split.txt", dtype=np.int32)
+def test_chairs_split_matches_reference_file():
+    ref = np.loadtxt(os.path.join(os.path.dirname(__file__), "golden", "chairs_split.txt"), dtype=np.int32)
     assert np.array_equal(chairs_split(), ref)

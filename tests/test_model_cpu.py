@@ -1,8 +1,12 @@
 """RAFT model on CPU: checkpoint schema, parity with the reference, API behaviour."""
 import argparse
+import os
 
+import numpy as np
 import pytest
 import torch
+
+import golden
 
 from raft_ros_amd.models import RAFT
 
@@ -51,17 +55,17 @@ def test_args_mutation_like_reference():
 
 @pytest.mark.reference
 @pytest.mark.parametrize("small", [True, False])
-def test_forward_parity_with_reference(reference_core, small):
-    torch.manual_seed(0)
-    ref = reference_core.RAFT(_args(small=small)).eval()
-    ours = RAFT(_args(small=small)).eval()
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    i1 = torch.rand(1, 3, 128, 160) * 255
-    i2 = torch.rand(1, 3, 128, 160) * 255
+def test_forward_parity_with_reference(small):
+    """Against the reference's recorded outputs (tests/golden/raft_parity_*.npz, written by
+    scripts/make_golden_parity.py from the same seed-0 weights and the same images)."""
+    fix = np.load(os.path.join(golden.GOLDEN, "raft_parity_%s.npz" % ("small" if small else "base")))
+    ck = {k[3:]: fix[k] for k in fix.files if k.startswith("ck/")}
+    ours = golden.parity_model(small, 0, ck).eval()
+    i1, i2 = golden.parity_helpers()[0](128, 160)
+    lo_r, up_r = torch.from_numpy(fix["flow_low"]), torch.from_numpy(fix["flow_up"])
+    preds_r = [torch.from_numpy(fix["pred0"]), torch.from_numpy(fix["pred1"])]
     with torch.no_grad():
-        lo_r, up_r = ref(i1, i2, iters=3, test_mode=True)
         lo, up = ours(i1, i2, iters=3, test_mode=True)
-        preds_r = ref(i1, i2, iters=2)
         preds = ours(i1, i2, iters=2)
     torch.testing.assert_close(up, up_r, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(lo, lo_r, rtol=1e-4, atol=1e-4)
@@ -71,20 +75,18 @@ def test_forward_parity_with_reference(reference_core, small):
 
 
 @pytest.mark.reference
-def test_backward_parity_with_reference(reference_core):
-    torch.manual_seed(1)
-    ref = reference_core.RAFT(_args(small=True)).train()
-    ours = RAFT(_args(small=True)).train()
-    ours.load_state_dict(ref.state_dict())
-    i1 = torch.rand(1, 3, 128, 128) * 255
-    i2 = torch.rand(1, 3, 128, 128) * 255
-    sum(p.abs().mean() for p in ref(i1, i2, iters=2)).backward()
+def test_backward_parity_with_reference():
+    """Every parameter gradient against the reference's recorded ones (tests/golden/raft_grads_small_*,
+    complete, from the same seed-1 weights and the same images)."""
+    gr, ck = golden.parity_grads()
+    ours = golden.parity_model(True, 1, ck).train()
+    i1, i2 = golden.parity_helpers()[0](128, 128)
     sum(p.abs().mean() for p in ours(i1, i2, iters=2)).backward()
-    gr = dict(ref.named_parameters())
+    assert set(gr) <= {n for n, _ in ours.named_parameters()}
     for n, p in ours.named_parameters():
-        if gr[n].grad is None:
+        if n not in gr:
             continue
-        torch.testing.assert_close(p.grad, gr[n].grad, rtol=2e-3, atol=1e-6)
+        torch.testing.assert_close(p.grad, gr[n].reshape(p.shape), rtol=2e-3, atol=1e-6)
 
 
 def test_warm_start_and_shapes():

@@ -1,4 +1,6 @@
 """Reference (PyTorch) ops and geometry utilities on CPU."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -78,19 +80,16 @@ def test_forward_interpolate_constant_flow():
 
 
 @pytest.mark.reference
-def test_flow_viz_matches_reference(reference_core):
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("ref_flow_viz", "/root/reference/core/utils/flow_viz.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+def test_flow_viz_matches_reference():
+    """Against the reference's recorded colour wheel and images (tests/golden/flow_viz.npz)."""
     from raft_ros_amd.utils import flow_viz
+    import golden
 
-    rng = np.random.default_rng(0)
-    flow = rng.normal(size=(37, 41, 2)).astype(np.float32) * 5
-    assert np.array_equal(flow_viz.make_colorwheel(), mod.make_colorwheel())
+    fix = np.load(os.path.join(golden.GOLDEN, "flow_viz.npz"))
+    flow = golden.parity_helpers()[1]()
+    assert np.array_equal(flow_viz.make_colorwheel(), fix["colorwheel"])
     for bgr in (False, True):
-        assert np.array_equal(flow_viz.flow_to_image(flow, convert_to_bgr=bgr), mod.flow_to_image(flow, convert_to_bgr=bgr))
+        assert np.array_equal(flow_viz.flow_to_image(flow, convert_to_bgr=bgr), fix["bgr" if bgr else "rgb"])
 
 
 def test_blocked_level_layout_matches_kernel_indexing():
