@@ -28,6 +28,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from raft_ros_amd.models import RAFT  # noqa: E402
+from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
 from raft_ros_amd.utils.utils import InputPadder  # noqa: E402
 
@@ -93,13 +94,19 @@ def demo(args):
     if not images:
         images = write_demo_frames(args.path)
     outs = []
+    warm = getattr(args, "warm_start", False)
+    flow_prev = None  # --warm_start: the last pair's low-resolution flow, projected onto its second frame
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
             image1 = load_image(imfile1, args.device)
             image2 = load_image(imfile2, args.device)
             padder = InputPadder(image1.shape)
             image1, image2 = padder.pad(image1, image2)
-            flow_low, flow_up = model(image1, image2, iters=args.iters, test_mode=True)
+            if flow_prev is not None and flow_prev.shape[-2:] != (image1.shape[-2] // 8, image1.shape[-1] // 8):
+                flow_prev = None  # the frame size changed: cold start
+            flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
+            if warm:
+                flow_prev = forward_splat_nearest(flow_low)
             out = os.path.join(args.output, "flow_%04d.png" % k)
             if rank == 0:
                 viz(image1, flow_up, out, show=args.show)
@@ -122,6 +129,9 @@ def main(argv=None):
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--output", default="demo-output")
     p.add_argument("--show", action="store_true", help="also display with cv2 (if available)")
+    p.add_argument("--warm_start", action="store_true",
+                   help="start every pair from the previous pair's flow, forward-projected on the device "
+                        "(consecutive pairs of the sorted directory are continuous)")
     p.add_argument("--query_shard", action="store_true",
                    help="under torchrun: shard the correlation volume over the ranks' query pixels "
                         "(high-resolution inference; raft_ros_amd/parallel/query_shard.py)")

@@ -618,6 +618,18 @@ inline bool up_seg_ok(unsigned long addr, int esz, long sN, long sC, long sH, lo
          (long)B * sN < (1L << 31) && (long)B * H * W * 128 < (1L << 31) && (long)sH * H <= sN;
 }
 
+// ============================================================================ warm start
+// Forward splat with nearest-neighbour fill (csrc/forward_splat.hip).  The workspace is one
+// int allocation of 2 * B * H * W + B words: heads, then any, then next.
+struct SplatArgs {
+  const float* flow;  // (B, 2, H, W) fp32
+  float* out;         // (B, 2, H, W) fp32
+  int* heads;         // [B][H * W] first source index of each cell's list, -1 = empty
+  int* any;           // [B] = heads + B * H * W: -1 while the image has no valid point
+  int* next;          // [B][H * W] next source index in the same cell, -1 = end
+  int B, H, W;
+};
+
 // ============================================================================ correlation build
 // Row tiles per group of the v2 volume build's tile order (cfg 2-5 force 1 / 2 / 4 / 16):
 // 8 while one image's B operand (N x K bf16) fits 8 MB, 4 beyond (the 1080p store stream).
@@ -653,6 +665,8 @@ RAFT_HD inline int corr_group_rows(long N, long K, int cfg) {
 namespace raft_amd {
 // optim.hip
 hipError_t launch_adamw(const AdamArgs& a, int nblk, bool update, hipStream_t s);
+// forward_splat.hip
+hipError_t launch_forward_splat(const SplatArgs& a, hipStream_t s);
 // conv_igemm.hip
 hipError_t launch_conv_fwd(const ConvFwdArgs& a, hipStream_t s);
 hipError_t launch_conv_wgrad(ConvWgradArgs a, const WgradPlan& pl, hipStream_t s);

@@ -4,7 +4,8 @@
   clean + final: EPE and 1/3/5 px rates, centred padding), ``validate_kitti``
   (24 iterations, bottom padding; EPE = mean of per-image means, F1 = % of
   valid pixels with epe > 3 and epe/|gt| > 0.05);
-* ``create_sintel_submission`` (optional warm start with ``forward_interpolate``)
+* ``create_sintel_submission`` (optional warm start: the device forward splat of
+  ``ops/warm_start.py`` on a GPU, ``forward_interpolate`` on the CPU)
   and ``create_kitti_submission``;
 * ``validate_synthetic`` -- the same EPE protocol on generated pairs with exact
   ground truth, for environments without the datasets.
@@ -24,6 +25,7 @@ import torch
 
 from ..data import datasets, frame_utils
 from ..data.synthetic import synthetic_batch
+from ..ops.warm_start import forward_splat_nearest
 from ..utils.utils import InputPadder, forward_interpolate
 
 
@@ -58,7 +60,9 @@ def create_sintel_submission(model, iters=32, warm_start=False, output_path="sin
             image1, image2 = padder.pad(image1[None].to(dev), image2[None].to(dev))
             flow_low, flow_pr = model(image1, image2, iters=iters, flow_init=flow_prev, test_mode=True)
             flow = padder.unpad(flow_pr[0]).permute(1, 2, 0).cpu().numpy()
-            if warm_start:
+            if warm_start and dev.type == "cuda":
+                flow_prev = forward_splat_nearest(flow_low)  # HIP splat: no host round trip
+            elif warm_start:
                 flow_prev = forward_interpolate(flow_low[0])[None].to(dev)
             output_dir = os.path.join(output_path, dstype, sequence)
             os.makedirs(output_dir, exist_ok=True)

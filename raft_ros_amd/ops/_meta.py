@@ -204,6 +204,10 @@ def register() -> None:
     def _(grad, H, W, rows):
         return grad.new_empty((grad.shape[0], 2, H, W))
 
+    @fake(lib + "forward_splat_nearest")
+    def _(flow):
+        return torch.empty_like(flow, memory_format=torch.contiguous_format)
+
     # mutating ops: nothing to infer
     for name in ("conv_fwd", "conv_wgrad", "conv_wgrad_params", "gru_bwd_a", "gru_bwd_b", "masked_cast",
                  "pack_flow", "apply_delta", "n2_apply", "corr_lookup_into", "corr_lookup_split_into", "convex_upsample_backward_into",

@@ -112,3 +112,41 @@ def local_corr(fmap1: torch.Tensor, fmap2: torch.Tensor, coords: torch.Tensor, r
     pts = c + window_offsets(radius, coords.device, coords.dtype)[None]
     out = bilinear_sampler(vol, pts)
     return out.reshape(B, H1, W1, -1).permute(0, 3, 1, 2)
+
+
+def forward_splat_nearest_ref(flow: torch.Tensor, return_gap: bool = False):
+    """Brute-force oracle of the warm-start forward splat (tests only: O((HW)^2)).
+
+    Source pixel ``s = y W + x`` with flow ``(dx, dy)`` is the point ``(x + dx, y + dy)`` in
+    fp64, valid iff ``0 < x1 < W`` and ``0 < y1 < H``; every target pixel takes the flow of
+    the valid point of least squared distance (fp64 all-pairs matrix, invalid columns +inf),
+    ``torch.argmin`` returning the first minimum, i.e. the lowest ``s``; an image without a
+    valid point gives zeros.  ``flow`` is (2, H, W) or (B, 2, H, W); the result is fp32 on the
+    CPU.  With ``return_gap`` also returns, per target pixel, the difference of the two
+    smallest squared distances ((H, W) or (B, H, W), fp64).
+    """
+    squeeze = flow.dim() == 3
+    f = (flow[None] if squeeze else flow).detach().cpu().float()
+    B, _, H, W = f.shape
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    xt, yt = xs.reshape(-1), ys.reshape(-1)
+    out = torch.zeros_like(f)
+    gap = torch.full((B, H, W), float("inf"), dtype=torch.float64)
+    for b in range(B):
+        dx, dy = f[b, 0].reshape(-1), f[b, 1].reshape(-1)
+        x1, y1 = xt + dx.double(), yt + dy.double()
+        valid = (x1 > 0) & (x1 < W) & (y1 > 0) & (y1 < H)
+        if not bool(valid.any()):
+            continue
+        ex, ey = x1[None, :] - xt[:, None], y1[None, :] - yt[:, None]
+        d2 = ex * ex + ey * ey  # (targets, sources)
+        d2[:, ~valid] = float("inf")
+        idx = torch.argmin(d2, dim=1)
+        out[b, 0], out[b, 1] = dx[idx].view(H, W), dy[idx].view(H, W)
+        if return_gap and d2.shape[1] > 1:
+            two = torch.topk(d2, 2, dim=1, largest=False).values
+            gap[b] = torch.nan_to_num(two[:, 1] - two[:, 0], nan=float("inf")).view(H, W)
+    out = out[0] if squeeze else out
+    if return_gap:
+        return out, (gap[0] if squeeze else gap)
+    return out

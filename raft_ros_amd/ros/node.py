@@ -7,7 +7,11 @@ Topics / parameters are those of the reference so existing launch files work:
   ``passthrough`` (BGR uint8), header = the *current* image's header with
   ``frame_id = "raft_image"``;
 * ``/RAFT/weight_path``, ``/RAFT/is_small``, ``/RAFT/device``; 20 refinement
-  iterations, fp32 (``mixed_precision = False``) unless ``/RAFT/mixed_precision``.
+  iterations unless ``/RAFT/iters``, fp32 (``mixed_precision = False``) unless
+  ``/RAFT/mixed_precision``;
+* ``/RAFT/warm_start`` (default off): a pair whose previous frame is the last pair's current
+  frame (equal stamps, same size) starts from that pair's flow, forward-projected on the
+  device (``ops/warm_start.py``).
 
 Pairing rule (reference :87-114): take the oldest current frame, then discard
 previous frames until one with a stamp strictly earlier than the current one is
@@ -32,6 +36,7 @@ import numpy as np
 import torch
 
 from ..models import RAFT
+from ..ops.warm_start import forward_splat_nearest
 from ..runtime import GraphedRAFT
 from ..utils import checkpoint, flow_viz
 from ..utils.utils import InputPadder
@@ -96,7 +101,7 @@ class FlowInference:
     """RAFT inference on numpy HxWx3 uint8 frames -> BGR uint8 flow visualisation."""
 
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
-                 mixed_precision: bool = False, hip_graph: bool = True):
+                 mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False):
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         self.device = torch.device(device)
@@ -108,21 +113,50 @@ class FlowInference:
         self.model.to(self.device).eval()
         # camera streams have a fixed frame size: capture the forward once, replay per pair
         self.runner = GraphedRAFT(self.model, iters=iters, enabled=hip_graph)
+        # warm start (video): the last pair's low-resolution flow, forward-projected onto its
+        # current frame, initialises the next pair when that pair starts at the same frame
+        self.warm_start = warm_start
+        self.reset_warm_start()
+
+    def reset_warm_start(self) -> None:
+        """Forget the previous pair: the next call runs cold."""
+        self._warm_flow: Optional[torch.Tensor] = None
+        self._warm_stamp = None
+        self._warm_shape = None
 
     @torch.inference_mode()
-    def flow(self, prev: np.ndarray, curr: np.ndarray) -> torch.Tensor:
+    def flow(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> torch.Tensor:
+        """Flow of the padded pair.  With ``warm_start`` the call is warm only when ``prev_stamp``
+        is given and equals the last call's ``curr_stamp`` and the padded shape is unchanged;
+        any other call runs cold and drops the kept state."""
         image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
         image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
         image1, image2 = image1.to(self.device), image2.to(self.device)
         padder = InputPadder(image1.shape)
         image1, image2 = padder.pad(image1, image2)
-        _, flow_up = self.runner(image1, image2)
+        if not self.warm_start:
+            _, flow_up = self.runner(image1, image2)
+            return flow_up
+        shape = tuple(image1.shape)
+        warm = (self._warm_flow is not None and prev_stamp is not None and prev_stamp == self._warm_stamp
+                and shape == self._warm_shape)
+        flow_init = self._warm_flow if warm else None
+        self.reset_warm_start()
+        if flow_init is None:
+            flow_low, flow_up = self.runner(image1, image2)
+        else:
+            flow_low, flow_up = self.runner(image1, image2, flow_init=flow_init)
+        if curr_stamp is not None:
+            # flow_low may be a captured graph's static output, overwritten by the next replay:
+            # the splat reads it now and writes a fresh tensor
+            self._warm_flow = forward_splat_nearest(flow_low)
+            self._warm_stamp, self._warm_shape = curr_stamp, shape
         return flow_up
 
-    def visualize(self, prev: np.ndarray, curr: np.ndarray) -> np.ndarray:
+    def visualize(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> np.ndarray:
         """The published image: colour-coded flow of the *padded* pair, BGR uint8
         (reference convert2Img + inferRAFT, ros/scripts/main.py:70-80,117-149)."""
-        flo = self.flow(prev, curr)[0].permute(1, 2, 0).float().cpu().numpy()
+        flo = self.flow(prev, curr, prev_stamp, curr_stamp)[0].permute(1, 2, 0).float().cpu().numpy()
         rgb = flow_viz.flow_to_image(flo)
         return np.ascontiguousarray(rgb[:, :, [2, 1, 0]]).astype(np.uint8)
 
@@ -144,12 +178,15 @@ class RaftRosNode:
         rospy.Subscriber(rospy.get_param("/ROS/prev_img"), image_msg, self.callbackPrevImage)
         rospy.Subscriber(rospy.get_param("/ROS/curr_img"), image_msg, self.callbackCurrImage)
         self._pub = rospy.Publisher("/raft_result", image_msg, queue_size=100)
+        self.warm_start = bool(_get_param(rospy, "/RAFT/warm_start", False))
         if inference is None:
             print("Initialize RAFT...")
             inference = FlowInference(rospy.get_param("/RAFT/weight_path"), bool(rospy.get_param("/RAFT/is_small")),
                                       str(rospy.get_param("/RAFT/device")),
+                                      iters=int(_get_param(rospy, "/RAFT/iters", 20)),
                                       mixed_precision=bool(_get_param(rospy, "/RAFT/mixed_precision", False)),
-                                      hip_graph=bool(_get_param(rospy, "/RAFT/hip_graph", True)))
+                                      hip_graph=bool(_get_param(rospy, "/RAFT/hip_graph", True)),
+                                      warm_start=self.warm_start)
             print("Initialize RAFT finish!")
         self.inference = inference
         self._thread: Optional[threading.Thread] = None
@@ -164,7 +201,11 @@ class RaftRosNode:
     def process_pair(self, prev_msg, curr_msg):
         prev = self.bridge.imgmsg_to_cv2(prev_msg, desired_encoding="passthrough")
         curr = self.bridge.imgmsg_to_cv2(curr_msg, desired_encoding="passthrough")
-        result = self.inference.visualize(np.asarray(prev), np.asarray(curr))
+        if self.warm_start:  # the message stamps tell the inference whether pairs are continuous
+            result = self.inference.visualize(np.asarray(prev), np.asarray(curr), prev_stamp=_stamp_sec(prev_msg),
+                                              curr_stamp=_stamp_sec(curr_msg))
+        else:
+            result = self.inference.visualize(np.asarray(prev), np.asarray(curr))
         header = curr_msg.header
         header.frame_id = "raft_image"
         out = self.bridge.cv2_to_imgmsg(result, encoding="passthrough", header=header)
