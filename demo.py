@@ -28,6 +28,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from raft_ros_amd.models import RAFT  # noqa: E402
+from raft_ros_amd.ops.frame_io import flow_to_image, ingest_frames  # noqa: E402
 from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
 from raft_ros_amd.utils.utils import InputPadder  # noqa: E402
@@ -35,17 +36,24 @@ from raft_ros_amd.utils.utils import InputPadder  # noqa: E402
 DEVICE = "cuda" if torch.cuda.is_available() else "cpu"
 
 
-def load_image(imfile, device=DEVICE):
+def load_image(imfile, device=DEVICE, raw=False):
+    """(1, 3, H, W) fp32 on ``device``; ``raw``: the (H, W, 3) uint8 frame itself, uploaded as it is."""
     img = np.array(Image.open(imfile).convert("RGB")).astype(np.uint8)
+    if raw:
+        return torch.from_numpy(img).to(device)
     img = torch.from_numpy(img).permute(2, 0, 1).float()
     return img[None].to(device)
 
 
-def viz(img, flo, out_path=None, show=False):
-    img = img[0].permute(1, 2, 0).cpu().numpy()
-    flo = flo[0].permute(1, 2, 0).cpu().numpy()
-    flo = flow_viz.flow_to_image(flo)
-    img_flo = np.concatenate([img, flo], axis=0).astype(np.uint8)
+def viz(img, flo, out_path=None, show=False, device_viz=False):
+    if device_viz:  # colour-code where the flow lives: only the uint8 [image; flow] comes back
+        img = img[0].permute(1, 2, 0).to(torch.uint8)
+        img_flo = torch.cat([img, flow_to_image(flo[0])], dim=0).cpu().numpy()
+    else:
+        img = img[0].permute(1, 2, 0).cpu().numpy()
+        flo = flo[0].permute(1, 2, 0).cpu().numpy()
+        flo = flow_viz.flow_to_image(flo)
+        img_flo = np.concatenate([img, flo], axis=0).astype(np.uint8)
     if out_path:
         Image.fromarray(img_flo).save(out_path)
     if show:
@@ -96,12 +104,18 @@ def demo(args):
     outs = []
     warm = getattr(args, "warm_start", False)
     flow_prev = None  # --warm_start: the last pair's low-resolution flow, projected onto its second frame
+    device_viz = getattr(args, "device_viz", False)
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
-            image1 = load_image(imfile1, args.device)
-            image2 = load_image(imfile2, args.device)
-            padder = InputPadder(image1.shape)
-            image1, image2 = padder.pad(image1, image2)
+            if device_viz:
+                pair, padder = ingest_frames([load_image(imfile1, args.device, raw=True),
+                                              load_image(imfile2, args.device, raw=True)])
+                image1, image2 = pair[0:1], pair[1:2]
+            else:
+                image1 = load_image(imfile1, args.device)
+                image2 = load_image(imfile2, args.device)
+                padder = InputPadder(image1.shape)
+                image1, image2 = padder.pad(image1, image2)
             if flow_prev is not None and flow_prev.shape[-2:] != (image1.shape[-2] // 8, image1.shape[-1] // 8):
                 flow_prev = None  # the frame size changed: cold start
             flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
@@ -109,7 +123,7 @@ def demo(args):
                 flow_prev = forward_splat_nearest(flow_low)
             out = os.path.join(args.output, "flow_%04d.png" % k)
             if rank == 0:
-                viz(image1, flow_up, out, show=args.show)
+                viz(image1, flow_up, out, show=args.show, device_viz=device_viz)
             outs.append(out)
     return outs
 
@@ -132,6 +146,9 @@ def main(argv=None):
     p.add_argument("--warm_start", action="store_true",
                    help="start every pair from the previous pair's flow, forward-projected on the device "
                         "(consecutive pairs of the sorted directory are continuous)")
+    p.add_argument("--device_viz", action="store_true",
+                   help="frames are uploaded as uint8 and converted and padded on the device, the flow is "
+                        "colour-coded on the device: only the uint8 image comes back (ops/frame_io.py)")
     p.add_argument("--query_shard", action="store_true",
                    help="under torchrun: shard the correlation volume over the ranks' query pixels "
                         "(high-resolution inference; raft_ros_amd/parallel/query_shard.py)")

@@ -630,6 +630,29 @@ struct SplatArgs {
   int B, H, W;
 };
 
+// ============================================================================ frame path
+// Colour coding of a flow field (csrc/flow_color.hip): the Middlebury wheel of
+// utils/flow_viz.py, normalised by each image's own largest radius.
+struct FlowColorArgs {
+  const float* flow;   // (B, 2, H, W) fp32
+  unsigned char* img;  // (B, H, W, 3) uint8, 4-byte aligned base
+  unsigned* rad_max;   // [B] bit pattern of the image's largest sqrt(u^2 + v^2), zeroed per call
+  float clip;          // clip both components to [0, clip] first when has_clip
+  int has_clip;
+  int bgr;  // channel order of the output: 0 = RGB, 1 = BGR
+  int B;
+  long HW;  // H * W
+};
+
+// uint8 (N, H, W, 3) camera frames -> fp32 (N, 3, H + pt + pb, W + pl + pr), replicate padded.
+struct IngestArgs {
+  const unsigned char* in;  // (N, H, W, 3) uint8
+  float* out;               // (N, 3, Hp, Wp) fp32
+  int N, H, W;
+  int pl, pt;  // left / top pad (right / bottom follow from Hp, Wp)
+  int Hp, Wp;
+};
+
 // ============================================================================ correlation build
 // Row tiles per group of the v2 volume build's tile order (cfg 2-5 force 1 / 2 / 4 / 16):
 // 8 while one image's B operand (N x K bf16) fits 8 MB, 4 beyond (the 1080p store stream).
@@ -667,6 +690,9 @@ namespace raft_amd {
 hipError_t launch_adamw(const AdamArgs& a, int nblk, bool update, hipStream_t s);
 // forward_splat.hip
 hipError_t launch_forward_splat(const SplatArgs& a, hipStream_t s);
+// flow_color.hip
+hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
+hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
 // conv_igemm.hip
 hipError_t launch_conv_fwd(const ConvFwdArgs& a, hipStream_t s);
 hipError_t launch_conv_wgrad(ConvWgradArgs a, const WgradPlan& pl, hipStream_t s);

@@ -7,6 +7,7 @@ numerical oracle in tests.
 """
 from ._ext import is_loaded, library_path, load_error, use_native  # noqa: F401
 from .corr import CorrPyramid, LocalCorrPyramid  # noqa: F401
+from .frame_io import flow_to_image, ingest_frames  # noqa: F401
 from .upsample import convex_upsample, upflow8  # noqa: F401
 from .warm_start import forward_splat_nearest  # noqa: F401
 from . import reference  # noqa: F401

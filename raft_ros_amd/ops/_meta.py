@@ -208,6 +208,16 @@ def register() -> None:
     def _(flow):
         return torch.empty_like(flow, memory_format=torch.contiguous_format)
 
+    @fake(lib + "flow_to_image")
+    def _(flow, clip_flow, bgr):
+        B, _, H, W = flow.shape
+        return flow.new_empty((B, H, W, 3), dtype=torch.uint8)
+
+    @fake(lib + "ingest_frames")
+    def _(frames, pad_l, pad_r, pad_t, pad_b):
+        N, H, W, _ = frames.shape
+        return frames.new_empty((N, 3, H + pad_t + pad_b, W + pad_l + pad_r), dtype=torch.float32)
+
     # mutating ops: nothing to infer
     for name in ("conv_fwd", "conv_wgrad", "conv_wgrad_params", "gru_bwd_a", "gru_bwd_b", "masked_cast",
                  "pack_flow", "apply_delta", "n2_apply", "corr_lookup_into", "corr_lookup_split_into", "convex_upsample_backward_into",

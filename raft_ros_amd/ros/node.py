@@ -11,7 +11,12 @@ Topics / parameters are those of the reference so existing launch files work:
   ``/RAFT/mixed_precision``;
 * ``/RAFT/warm_start`` (default off): a pair whose previous frame is the last pair's current
   frame (equal stamps, same size) starts from that pair's flow, forward-projected on the
-  device (``ops/warm_start.py``).
+  device (``ops/warm_start.py``);
+* ``/RAFT/device_io`` (default off): on a GPU device the frames are uploaded as they arrive
+  (uint8, HWC; a quarter of the fp32 upload) and converted and padded by one HIP launch, and
+  the flow is colour-coded on the device, so that only the uint8 image comes back
+  (``ops/frame_io.py``).  The flow is bitwise the same; the image may differ from the numpy
+  colour coding by one level on rare pixels.  On a CPU device the parameter changes nothing.
 
 Pairing rule (reference :87-114): take the oldest current frame, then discard
 previous frames until one with a stamp strictly earlier than the current one is
@@ -36,6 +41,7 @@ import numpy as np
 import torch
 
 from ..models import RAFT
+from ..ops.frame_io import flow_to_image, ingest_frames
 from ..ops.warm_start import forward_splat_nearest
 from ..runtime import GraphedRAFT
 from ..utils import checkpoint, flow_viz
@@ -101,7 +107,8 @@ class FlowInference:
     """RAFT inference on numpy HxWx3 uint8 frames -> BGR uint8 flow visualisation."""
 
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
-                 mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False):
+                 mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False,
+                 device_io: bool = False):
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         self.device = torch.device(device)
@@ -117,6 +124,12 @@ class FlowInference:
         # current frame, initialises the next pair when that pair starts at the same frame
         self.warm_start = warm_start
         self.reset_warm_start()
+        # device-side frame path (GPU only): uint8 upload + HIP ingest, HIP colour coding; the
+        # pinned staging buffers are kept while the frame size stays the same
+        self.device_io = device_io
+        self._pin_in: Optional[torch.Tensor] = None
+        self._pin_in_free: Optional[torch.cuda.Event] = None
+        self._pin_out: Optional[torch.Tensor] = None
 
     def reset_warm_start(self) -> None:
         """Forget the previous pair: the next call runs cold."""
@@ -124,16 +137,42 @@ class FlowInference:
         self._warm_stamp = None
         self._warm_shape = None
 
+    @property
+    def _on_device(self) -> bool:
+        return self.device_io and self.device.type == "cuda"
+
+    def _ingest(self, prev: np.ndarray, curr: np.ndarray):
+        """The pair as uint8 through one pinned buffer -> the padded fp32 images on the device."""
+        a = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8))
+        b = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8))
+        if a.shape != b.shape or a.dim() != 3:
+            raise ValueError(f"frames must be two (H, W, 3) images of one size, got {tuple(a.shape)}, {tuple(b.shape)}")
+        if self._pin_in is None or self._pin_in.shape[1:] != a.shape:
+            self._pin_in = torch.empty((2,) + tuple(a.shape), dtype=torch.uint8, pin_memory=True)
+            self._pin_in_free = torch.cuda.Event()
+        else:
+            self._pin_in_free.synchronize()  # the last pair's upload has read the buffer
+        self._pin_in[0].copy_(a)
+        self._pin_in[1].copy_(b)
+        with torch.cuda.device(self.device):
+            frames = self._pin_in.to(self.device, non_blocking=True)
+            self._pin_in_free.record()
+        images, _ = ingest_frames(frames)
+        return images[0:1], images[1:2]
+
     @torch.inference_mode()
     def flow(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> torch.Tensor:
         """Flow of the padded pair.  With ``warm_start`` the call is warm only when ``prev_stamp``
         is given and equals the last call's ``curr_stamp`` and the padded shape is unchanged;
         any other call runs cold and drops the kept state."""
-        image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
-        image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
-        image1, image2 = image1.to(self.device), image2.to(self.device)
-        padder = InputPadder(image1.shape)
-        image1, image2 = padder.pad(image1, image2)
+        if self._on_device:
+            image1, image2 = self._ingest(prev, curr)
+        else:
+            image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
+            image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
+            image1, image2 = image1.to(self.device), image2.to(self.device)
+            padder = InputPadder(image1.shape)
+            image1, image2 = padder.pad(image1, image2)
         if not self.warm_start:
             _, flow_up = self.runner(image1, image2)
             return flow_up
@@ -156,6 +195,14 @@ class FlowInference:
     def visualize(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> np.ndarray:
         """The published image: colour-coded flow of the *padded* pair, BGR uint8
         (reference convert2Img + inferRAFT, ros/scripts/main.py:70-80,117-149)."""
+        if self._on_device:
+            with torch.inference_mode():
+                img = flow_to_image(self.flow(prev, curr, prev_stamp, curr_stamp), convert_to_bgr=True)[0]
+                if self._pin_out is None or self._pin_out.shape != img.shape:
+                    self._pin_out = torch.empty(tuple(img.shape), dtype=torch.uint8, pin_memory=True)
+                self._pin_out.copy_(img, non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+            return self._pin_out.numpy().copy()  # the buffer is reused: the caller gets its own memory
         flo = self.flow(prev, curr, prev_stamp, curr_stamp)[0].permute(1, 2, 0).float().cpu().numpy()
         rgb = flow_viz.flow_to_image(flo)
         return np.ascontiguousarray(rgb[:, :, [2, 1, 0]]).astype(np.uint8)
@@ -186,7 +233,8 @@ class RaftRosNode:
                                       iters=int(_get_param(rospy, "/RAFT/iters", 20)),
                                       mixed_precision=bool(_get_param(rospy, "/RAFT/mixed_precision", False)),
                                       hip_graph=bool(_get_param(rospy, "/RAFT/hip_graph", True)),
-                                      warm_start=self.warm_start)
+                                      warm_start=self.warm_start,
+                                      device_io=bool(_get_param(rospy, "/RAFT/device_io", False)))
             print("Initialize RAFT finish!")
         self.inference = inference
         self._thread: Optional[threading.Thread] = None
