@@ -11,8 +11,11 @@ Runs every consecutive pair of *.png / *.jpg frames in ``--path`` (sorted) with
 20 refinement iterations.  The reference shows [image; flow] in a cv2 window;
 here the visualisation is shown with cv2 when it is importable and a display is
 available, and is always written to ``--output`` (default ``demo-output/``) as
-PNG.  ``--model`` is optional (random weights) so the pipeline can be smoke-
-tested without the pretrained files.
+PNG.  With ``--occlusion`` every pair also runs backwards (one batch of two) and the
+forward-backward consistency mask is written beside the flow as ``occ_%04d.png``
+(0 consistent, 128 inconsistent, 255 the flow leaves the frame).  ``--model`` is
+optional (random weights) so the pipeline can be smoke-tested without the
+pretrained files.
 """
 from __future__ import annotations
 
@@ -28,6 +31,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from raft_ros_amd.models import RAFT  # noqa: E402
+from raft_ros_amd.ops.consistency import OCC_LEVELS, fb_consistency  # noqa: E402
 from raft_ros_amd.ops.frame_io import flow_to_image, ingest_frames  # noqa: E402
 from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
@@ -105,6 +109,7 @@ def demo(args):
     warm = getattr(args, "warm_start", False)
     flow_prev = None  # --warm_start: the last pair's low-resolution flow, projected onto its second frame
     device_viz = getattr(args, "device_viz", False)
+    occlusion = getattr(args, "occlusion", False)
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
             if device_viz:
@@ -118,7 +123,19 @@ def demo(args):
                 image1, image2 = padder.pad(image1, image2)
             if flow_prev is not None and flow_prev.shape[-2:] != (image1.shape[-2] // 8, image1.shape[-1] // 8):
                 flow_prev = None  # the frame size changed: cold start
-            flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
+            if occlusion:
+                # both directions as one batch of the pair and the swapped pair; the backward
+                # direction has no previous flow and always starts cold
+                init = None if flow_prev is None else torch.cat([flow_prev, torch.zeros_like(flow_prev)])
+                flow_low, flow_up = model(torch.cat([image1, image2]), torch.cat([image2, image1]), iters=args.iters,
+                                          flow_init=init, test_mode=True)
+                occ = fb_consistency(flow_up[0:1], flow_up[1:2])[0]
+                flow_low, flow_up = flow_low[0:1], flow_up[0:1]
+                if rank == 0:  # mono mask: 0 consistent, 128 inconsistent, 255 the flow leaves the frame
+                    mask = OCC_LEVELS[occ[0].cpu().numpy()]
+                    Image.fromarray(mask, mode="L").save(os.path.join(args.output, "occ_%04d.png" % k))
+            else:
+                flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
             if warm:
                 flow_prev = forward_splat_nearest(flow_low)
             out = os.path.join(args.output, "flow_%04d.png" % k)
@@ -149,6 +166,10 @@ def main(argv=None):
     p.add_argument("--device_viz", action="store_true",
                    help="frames are uploaded as uint8 and converted and padded on the device, the flow is "
                         "colour-coded on the device: only the uint8 image comes back (ops/frame_io.py)")
+    p.add_argument("--occlusion", action="store_true",
+                   help="run every pair in both directions (one batch of two) and write the forward-backward "
+                        "consistency mask as occ_%%04d.png beside the flow: 0 consistent, 128 inconsistent, "
+                        "255 the flow leaves the frame (ops/consistency.py)")
     p.add_argument("--query_shard", action="store_true",
                    help="under torchrun: shard the correlation volume over the ranks' query pixels "
                         "(high-resolution inference; raft_ros_amd/parallel/query_shard.py)")

@@ -653,6 +653,19 @@ struct IngestArgs {
   int Hp, Wp;
 };
 
+// Forward-backward consistency of a flow pair (csrc/fb_consistency.hip): follow the forward
+// flow, read the backward flow there bilinearly; the two should cancel.
+struct FbConsistencyArgs {
+  const float* fw;     // (B, 2, H, W) fp32 forward flow
+  const float* bw;     // (B, 2, H, W) fp32 backward flow
+  unsigned char* occ;  // (B, H, W) uint8, 4-byte aligned base: 0 consistent, 1 inconsistent, 2 leaves the frame
+  float* err2;         // (B, H, W) fp32, 16-byte aligned base: |fw + bw(target)|^2, +inf for class 2
+  int* counts;         // [B][2] pixels of class 1 and of class 2, zeroed per call
+  float alpha1, alpha2;
+  int B, H, W;
+  long HW;  // H * W
+};
+
 // ============================================================================ correlation build
 // Row tiles per group of the v2 volume build's tile order (cfg 2-5 force 1 / 2 / 4 / 16):
 // 8 while one image's B operand (N x K bf16) fits 8 MB, 4 beyond (the 1080p store stream).
@@ -693,6 +706,8 @@ hipError_t launch_forward_splat(const SplatArgs& a, hipStream_t s);
 // flow_color.hip
 hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
 hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
+// fb_consistency.hip
+hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
 // conv_igemm.hip
 hipError_t launch_conv_fwd(const ConvFwdArgs& a, hipStream_t s);
 hipError_t launch_conv_wgrad(ConvWgradArgs a, const WgradPlan& pl, hipStream_t s);

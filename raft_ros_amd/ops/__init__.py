@@ -6,6 +6,7 @@
 numerical oracle in tests.
 """
 from ._ext import is_loaded, library_path, load_error, use_native  # noqa: F401
+from .consistency import fb_consistency, fb_consistency_ref  # noqa: F401
 from .corr import CorrPyramid, LocalCorrPyramid  # noqa: F401
 from .frame_io import flow_to_image, ingest_frames  # noqa: F401
 from .upsample import convex_upsample, upflow8  # noqa: F401

@@ -218,6 +218,12 @@ def register() -> None:
         N, H, W, _ = frames.shape
         return frames.new_empty((N, 3, H + pad_t + pad_b, W + pad_l + pad_r), dtype=torch.float32)
 
+    @fake(lib + "fb_consistency")
+    def _(flow_fw, flow_bw, alpha1, alpha2):
+        B, _, H, W = flow_fw.shape
+        return (flow_fw.new_empty((B, H, W), dtype=torch.uint8), flow_fw.new_empty((B, H, W), dtype=torch.float32),
+                flow_fw.new_empty((B, 2), dtype=torch.int32))
+
     # mutating ops: nothing to infer
     for name in ("conv_fwd", "conv_wgrad", "conv_wgrad_params", "gru_bwd_a", "gru_bwd_b", "masked_cast",
                  "pack_flow", "apply_delta", "n2_apply", "corr_lookup_into", "corr_lookup_split_into", "convex_upsample_backward_into",

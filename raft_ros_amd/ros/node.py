@@ -17,6 +17,11 @@ Topics / parameters are those of the reference so existing launch files work:
   the flow is colour-coded on the device, so that only the uint8 image comes back
   (``ops/frame_io.py``).  The flow is bitwise the same; the image may differ from the numpy
   colour coding by one level on rare pixels.  On a CPU device the parameter changes nothing.
+* ``/RAFT/occlusion`` (default off): the flow is computed in both directions (one batch of the
+  pair and the swapped pair) and checked forward against backward (``ops/consistency.py``); the
+  mask is published on ``/raft_occlusion`` (queue_size 100), encoding ``mono8``, with the header
+  of the result: 0 = consistent, 128 = inconsistent (occluded or mismatched), 255 = the flow
+  leaves the frame.  With the parameter off there is no second publisher.
 
 Pairing rule (reference :87-114): take the oldest current frame, then discard
 previous frames until one with a stamp strictly earlier than the current one is
@@ -41,6 +46,7 @@ import numpy as np
 import torch
 
 from ..models import RAFT
+from ..ops.consistency import OCC_LEVELS, fb_consistency
 from ..ops.frame_io import flow_to_image, ingest_frames
 from ..ops.warm_start import forward_splat_nearest
 from ..runtime import GraphedRAFT
@@ -108,7 +114,7 @@ class FlowInference:
 
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
                  mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False,
-                 device_io: bool = False):
+                 device_io: bool = False, consistency: bool = False):
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         self.device = torch.device(device)
@@ -130,6 +136,12 @@ class FlowInference:
         self._pin_in: Optional[torch.Tensor] = None
         self._pin_in_free: Optional[torch.cuda.Event] = None
         self._pin_out: Optional[torch.Tensor] = None
+        # bidirectional mode (flow_checked / visualize_checked): the pair and the swapped pair as
+        # one batch of two, then the forward-backward check of ops/consistency.py
+        self.consistency = consistency
+        self.last_counts: Optional[np.ndarray] = None  # pixels of class 1 / 2 of the last visualize_checked
+        self._pin_occ: Optional[torch.Tensor] = None
+        self._pin_counts: Optional[torch.Tensor] = None
 
     def reset_warm_start(self) -> None:
         """Forget the previous pair: the next call runs cold."""
@@ -160,23 +172,27 @@ class FlowInference:
         images, _ = ingest_frames(frames)
         return images[0:1], images[1:2]
 
-    @torch.inference_mode()
-    def flow(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> torch.Tensor:
-        """Flow of the padded pair.  With ``warm_start`` the call is warm only when ``prev_stamp``
-        is given and equals the last call's ``curr_stamp`` and the padded shape is unchanged;
-        any other call runs cold and drops the kept state."""
+    def _padded_pair(self, prev: np.ndarray, curr: np.ndarray):
+        """The two frames as the model takes them: (1, 3, Hp, Wp) fp32 on the device, padded."""
         if self._on_device:
-            image1, image2 = self._ingest(prev, curr)
-        else:
-            image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
-            image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
-            image1, image2 = image1.to(self.device), image2.to(self.device)
-            padder = InputPadder(image1.shape)
-            image1, image2 = padder.pad(image1, image2)
+            return self._ingest(prev, curr)
+        image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
+        image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
+        image1, image2 = image1.to(self.device), image2.to(self.device)
+        padder = InputPadder(image1.shape)
+        return padder.pad(image1, image2)
+
+    def _run(self, image1, image2, prev_stamp, curr_stamp, both: bool = False) -> torch.Tensor:
+        """flow_up of the padded pair, or with ``both`` of the batch [pair, swapped pair].  With
+        ``warm_start`` the call is warm only when ``prev_stamp`` is given and equals the last call's
+        ``curr_stamp`` and the padded shape is unchanged; any other call runs cold and drops the
+        kept state.  The kept state is the forward direction's alone."""
+        shape = tuple(image1.shape)
+        if both:
+            image1, image2 = torch.cat([image1, image2]), torch.cat([image2, image1])
         if not self.warm_start:
             _, flow_up = self.runner(image1, image2)
             return flow_up
-        shape = tuple(image1.shape)
         warm = (self._warm_flow is not None and prev_stamp is not None and prev_stamp == self._warm_stamp
                 and shape == self._warm_shape)
         flow_init = self._warm_flow if warm else None
@@ -184,13 +200,63 @@ class FlowInference:
         if flow_init is None:
             flow_low, flow_up = self.runner(image1, image2)
         else:
+            if both:  # the backward direction has no previous flow: it always starts cold
+                flow_init = torch.cat([flow_init, torch.zeros_like(flow_init)])
             flow_low, flow_up = self.runner(image1, image2, flow_init=flow_init)
         if curr_stamp is not None:
             # flow_low may be a captured graph's static output, overwritten by the next replay:
             # the splat reads it now and writes a fresh tensor
-            self._warm_flow = forward_splat_nearest(flow_low)
+            self._warm_flow = forward_splat_nearest(flow_low[0:1])
             self._warm_stamp, self._warm_shape = curr_stamp, shape
         return flow_up
+
+    @torch.inference_mode()
+    def flow(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> torch.Tensor:
+        """Flow of the padded pair.  With ``warm_start`` the call is warm only when ``prev_stamp``
+        is given and equals the last call's ``curr_stamp`` and the padded shape is unchanged;
+        any other call runs cold and drops the kept state."""
+        return self._run(*self._padded_pair(prev, curr), prev_stamp, curr_stamp)
+
+    @torch.inference_mode()
+    def flow_checked(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
+        """Bidirectional mode: (flow_fw, occ, err2, counts) of the padded pair.
+
+        The model runs once on the batch of the pair and the swapped pair; image 0 of its output is
+        the forward flow (what ``flow()`` computes), image 1 the backward flow, and
+        ``ops.consistency.fb_consistency`` checks one against the other.  With ``warm_start`` the
+        pairing rule is ``flow()``'s; only the forward direction is kept and only it starts warm."""
+        if not self.consistency:
+            raise RuntimeError("flow_checked needs FlowInference(consistency=True)")
+        flow_up = self._run(*self._padded_pair(prev, curr), prev_stamp, curr_stamp, both=True)
+        flow_fw = flow_up[0:1]
+        occ, err2, counts = fb_consistency(flow_fw, flow_up[1:2])
+        return flow_fw, occ, err2, counts
+
+    def visualize_checked(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
+        """(the image ``visualize`` returns, the mask as mono uint8 (H, W): 0 consistent, 128
+        inconsistent, 255 the flow leaves the frame).  The counts of the two classes are kept as
+        ``last_counts``.  With ``device_io`` everything comes back through pinned buffers under
+        one synchronisation."""
+        if self._on_device:
+            with torch.inference_mode():
+                flow_fw, occ, _, counts = self.flow_checked(prev, curr, prev_stamp, curr_stamp)
+                img = flow_to_image(flow_fw, convert_to_bgr=True)[0]
+                if self._pin_out is None or self._pin_out.shape != img.shape:
+                    self._pin_out = torch.empty(tuple(img.shape), dtype=torch.uint8, pin_memory=True)
+                if self._pin_occ is None or self._pin_occ.shape != occ.shape[1:]:
+                    self._pin_occ = torch.empty(tuple(occ.shape[1:]), dtype=torch.uint8, pin_memory=True)
+                    self._pin_counts = torch.empty((2,), dtype=torch.int32, pin_memory=True)
+                self._pin_out.copy_(img, non_blocking=True)
+                self._pin_occ.copy_(occ[0], non_blocking=True)
+                self._pin_counts.copy_(counts[0], non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+            self.last_counts = self._pin_counts.numpy().copy()
+            # the buffers are reused: the caller gets its own memory (the level look-up writes a new array)
+            return self._pin_out.numpy().copy(), OCC_LEVELS[self._pin_occ.numpy()]
+        flow_fw, occ, _, counts = self.flow_checked(prev, curr, prev_stamp, curr_stamp)
+        rgb = flow_viz.flow_to_image(flow_fw[0].permute(1, 2, 0).float().cpu().numpy())
+        self.last_counts = counts[0].cpu().numpy().copy()
+        return np.ascontiguousarray(rgb[:, :, [2, 1, 0]]).astype(np.uint8), OCC_LEVELS[occ[0].cpu().numpy()]
 
     def visualize(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> np.ndarray:
         """The published image: colour-coded flow of the *padded* pair, BGR uint8
@@ -226,6 +292,8 @@ class RaftRosNode:
         rospy.Subscriber(rospy.get_param("/ROS/curr_img"), image_msg, self.callbackCurrImage)
         self._pub = rospy.Publisher("/raft_result", image_msg, queue_size=100)
         self.warm_start = bool(_get_param(rospy, "/RAFT/warm_start", False))
+        self.occlusion = bool(_get_param(rospy, "/RAFT/occlusion", False))
+        self._pub_occ = rospy.Publisher("/raft_occlusion", image_msg, queue_size=100) if self.occlusion else None
         if inference is None:
             print("Initialize RAFT...")
             inference = FlowInference(rospy.get_param("/RAFT/weight_path"), bool(rospy.get_param("/RAFT/is_small")),
@@ -234,7 +302,8 @@ class RaftRosNode:
                                       mixed_precision=bool(_get_param(rospy, "/RAFT/mixed_precision", False)),
                                       hip_graph=bool(_get_param(rospy, "/RAFT/hip_graph", True)),
                                       warm_start=self.warm_start,
-                                      device_io=bool(_get_param(rospy, "/RAFT/device_io", False)))
+                                      device_io=bool(_get_param(rospy, "/RAFT/device_io", False)),
+                                      consistency=self.occlusion)
             print("Initialize RAFT finish!")
         self.inference = inference
         self._thread: Optional[threading.Thread] = None
@@ -249,15 +318,19 @@ class RaftRosNode:
     def process_pair(self, prev_msg, curr_msg):
         prev = self.bridge.imgmsg_to_cv2(prev_msg, desired_encoding="passthrough")
         curr = self.bridge.imgmsg_to_cv2(curr_msg, desired_encoding="passthrough")
-        if self.warm_start:  # the message stamps tell the inference whether pairs are continuous
-            result = self.inference.visualize(np.asarray(prev), np.asarray(curr), prev_stamp=_stamp_sec(prev_msg),
-                                              curr_stamp=_stamp_sec(curr_msg))
+        # the message stamps tell the inference whether pairs are continuous
+        stamps = dict(prev_stamp=_stamp_sec(prev_msg), curr_stamp=_stamp_sec(curr_msg)) if self.warm_start else {}
+        occ = None
+        if self.occlusion:
+            result, occ = self.inference.visualize_checked(np.asarray(prev), np.asarray(curr), **stamps)
         else:
-            result = self.inference.visualize(np.asarray(prev), np.asarray(curr))
+            result = self.inference.visualize(np.asarray(prev), np.asarray(curr), **stamps)
         header = curr_msg.header
         header.frame_id = "raft_image"
         out = self.bridge.cv2_to_imgmsg(result, encoding="passthrough", header=header)
         self._pub.publish(out)
+        if occ is not None:
+            self._pub_occ.publish(self.bridge.cv2_to_imgmsg(occ, encoding="mono8", header=header))
         return out
 
     def thdInference(self, stop: Optional[Callable[[], bool]] = None) -> None:
