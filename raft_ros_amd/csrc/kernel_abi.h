@@ -666,6 +666,45 @@ struct FbConsistencyArgs {
   long HW;  // H * W
 };
 
+// Training augmentation of a padded batch (csrc/augment.hip): colour jitter, eraser and the
+// resize / flip / crop warp of data/augment.py.  The drawn parameters of sample b are the rows
+// pf[b] (fp32) and pi[b] (int32), laid out by the offsets below (ops/augment.py packs them).
+constexpr int kAugF1 = 0;     // pf: image 1's factors (brightness, contrast, saturation, hue shift)
+constexpr int kAugF2 = 4;     // pf: image 2's (equal to image 1's unless asymmetric)
+constexpr int kAugSx = 8;     // pf: resize factors, 1 when the sample is not resized
+constexpr int kAugSy = 9;
+constexpr int kAugPF = 10;    // floats per sample
+constexpr int kAugO1 = 0;     // pi: image 1's round order, a permutation of 0..3
+constexpr int kAugO2 = 4;     // pi: image 2's
+constexpr int kAugAsym = 8;   // pi: 1 = each image has its own contrast mean, 0 = one over the pair
+constexpr int kAugNbox = 9;   // pi: active eraser boxes, 0..2
+constexpr int kAugBox = 10;   // pi: two boxes (x0, y0, dx, dy)
+constexpr int kAugRh = 18;    // pi: resized height and width
+constexpr int kAugRw = 19;
+constexpr int kAugHflip = 20;
+constexpr int kAugVflip = 21;
+constexpr int kAugX0 = 22;    // pi: crop origin in the resized (flipped) image
+constexpr int kAugY0 = 23;
+constexpr int kAugPI = 24;    // ints per sample
+constexpr int kAugStats = 8;  // 64-bit words of statistics per sample (5 used)
+
+struct AugmentArgs {
+  const unsigned char* img1;  // (B, Hm, Wm, 3) uint8, zero padded
+  const unsigned char* img2;
+  const float* flow;          // (B, Hm, Wm, 2) fp32, 8-byte aligned base
+  const long* size;           // (B, 2) the (h, w) region of each sample; clamped to (Hm, Wm)
+  const float* pf;            // (B, kAugPF)
+  const int* pi;              // (B, kAugPI)
+  unsigned* jit1;             // (B, Hm, Wm) workspace: the jittered images, r | g << 8 | b << 16,
+  unsigned* jit2;             //   written inside the regions only
+  long long* stats;           // (B, kAugStats) workspace, zeroed per call
+  float* out1;                // (B, 3, ch, cw) fp32, 16-byte aligned bases
+  float* out2;
+  float* oflow;               // (B, 2, ch, cw)
+  float* ovalid;              // (B, ch, cw)
+  int B, Hm, Wm, ch, cw;
+};
+
 // ============================================================================ correlation build
 // Row tiles per group of the v2 volume build's tile order (cfg 2-5 force 1 / 2 / 4 / 16):
 // 8 while one image's B operand (N x K bf16) fits 8 MB, 4 beyond (the 1080p store stream).
@@ -708,6 +747,8 @@ hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
 hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
 // fb_consistency.hip
 hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
+// augment.hip
+hipError_t launch_augment_batch(const AugmentArgs& a, hipStream_t s);
 // conv_igemm.hip
 hipError_t launch_conv_fwd(const ConvFwdArgs& a, hipStream_t s);
 hipError_t launch_conv_wgrad(ConvWgradArgs a, const WgradPlan& pl, hipStream_t s);

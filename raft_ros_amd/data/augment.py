@@ -3,7 +3,9 @@
 The reference augments one sample at a time on the CPU, inside DataLoader
 workers, with OpenCV and torchvision (core/utils/augmentor.py:15-246).  Here
 the workers only decode files; a whole padded batch is augmented on the GPU
-(or on the CPU for tests / single samples) with a handful of tensor ops:
+(or on the CPU for tests / single samples) with tensor ops, or on the GPU with
+``BatchAugmentor(native=True)`` by the HIP op ``raft_amd::augment_batch``
+(csrc/augment.hip, ops/augment.py) that computes the same:
 
 * photometric: ColorJitter with the PIL semantics of torchvision (random order
   of brightness / contrast / saturation / hue, each result rounded to uint8),
@@ -94,17 +96,21 @@ def _hsv_to_rgb(h, s, v):
     return torch.stack([r, g, b], 1)
 
 
-def _masked_mean(x, mask):
-    """Mean of (B, C, H, W) over the valid region mask (B, 1, H, W)."""
-    return (x * mask).sum((2, 3), keepdim=True) / mask.sum((2, 3), keepdim=True).clamp_min(1)
+def _masked_mean(x, mask, dtype=torch.float32):
+    """Mean of (B, C, H, W) over the valid region mask (B, 1, H, W), summed and divided in
+    ``dtype`` (the result has that dtype)."""
+    return ((x * mask).sum((2, 3), keepdim=True, dtype=dtype) /
+            mask.sum((2, 3), keepdim=True, dtype=dtype).clamp_min(1))
 
 
-def color_jitter(img: torch.Tensor, mask: torch.Tensor, factors: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+def color_jitter(img: torch.Tensor, mask: torch.Tensor, factors: torch.Tensor, order: torch.Tensor,
+                 mean_dtype=torch.float32) -> torch.Tensor:
     """torchvision ColorJitter (PIL backend) on a batch.
 
     img (B, 3, H, W) float in [0, 255]; mask (B, 1, H, W) valid region (means are over
     it); factors (B, 4) = (brightness, contrast, saturation, hue shift); order (B, 4) a
-    permutation of 0..3 per sample.
+    permutation of 0..3 per sample; mean_dtype: what the contrast round's luma mean is
+    accumulated in.
     """
     B = img.shape[0]
     for k in range(4):
@@ -113,7 +119,7 @@ def color_jitter(img: torch.Tensor, mask: torch.Tensor, factors: torch.Tensor, o
         f = factors.gather(1, op[:, None])[:, 0].view(B, 1, 1, 1)
         # all four candidates, selected per sample (a batch applies different ops per round)
         bright = _q8(img * f)
-        m = torch.floor(_masked_mean(_gray(img), mask) + 0.5)  # PIL: int(mean(L) + 0.5)
+        m = torch.floor(_masked_mean(_gray(img), mask, mean_dtype) + 0.5).to(img.dtype)  # PIL: int(mean(L) + 0.5)
         contrast = _q8(m + f * (img - m))
         gray = _q8(_gray(img))
         sat = _q8(gray + f * (img - gray))
@@ -135,12 +141,13 @@ class BatchAugmentor:
     batch's device: images (B, 3, ch, cw) in [0, 255], flow (B, 2, ch, cw), valid (B, ch, cw).
     """
 
-    def __init__(self, specs: Sequence[AugSpec], seed: int = 0, device="cpu"):
+    def __init__(self, specs: Sequence[AugSpec], seed: int = 0, device="cpu", native: bool = False):
         self.specs = list(specs)
         crops = {tuple(s.crop_size) for s in self.specs}
         assert len(crops) == 1, f"one crop size per mixture, got {crops}"
         self.crop = crops.pop()
         self.device = torch.device(device)
+        self.native = bool(native)  # GPU batches: apply() runs the HIP op raft_amd::augment_batch
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed))
 
@@ -169,20 +176,21 @@ class BatchAugmentor:
 
     @torch.no_grad()
     def __call__(self, batch: Dict[str, torch.Tensor]):
-        img1 = batch["img1"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
-        img2 = batch["img2"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
-        flow = batch["flow"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
-        valid = batch["valid"].to(self.device, non_blocking=True).float()
+        return self.apply(batch, self.draw(batch))
+
+    @torch.no_grad()
+    def draw(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Every random choice for one batch, as per-sample tensors on the augmentor's device:
+        ``f1, o1, f2, o2`` (B, 4) jitter factors and round orders of the two images (those of
+        image 1 again unless ``asym``), ``erase``, ``nbox`` and ``boxes`` (B, 2, 4) =
+        (x0, y0, dx, dy), the resize factors ``sx, sy`` (1 unless ``resize``), the resized size
+        ``rh, rw``, ``hflip, vflip``, the crop origin ``x0, y0`` and ``sparse``."""
         sizes = batch["size"].to(self.device)
         spec = batch["spec"].to(self.device)
-        B, _, Hm, Wm = img1.shape
-        dev = img1.device
+        B, dev = sizes.shape[0], sizes.device
         gen = self.gen
         p = self._params(spec)
         hs, ws = sizes[:, 0], sizes[:, 1]
-        yy = torch.arange(Hm, device=dev).view(1, 1, Hm, 1)
-        xx = torch.arange(Wm, device=dev).view(1, 1, 1, Wm)
-        region = ((yy < hs.view(B, 1, 1, 1)) & (xx < ws.view(B, 1, 1, 1))).float()
 
         # ---- photometric: asymmetric per image (p) or symmetric on the stacked pair
         asym = torch.rand(B, generator=gen, device=dev) < p["asym_prob"]
@@ -190,31 +198,17 @@ class BatchAugmentor:
         f2, o2 = self._factors(p["jitter"])
         f2 = torch.where(asym[:, None], f2, f1)
         o2 = torch.where(asym[:, None], o2, o1)
-        # symmetric: PIL sees img1 stacked over img2, so the contrast mean spans both images
-        pair = torch.cat([img1, img2], 2)
-        pmask = torch.cat([region, region], 2)
-        sym = color_jitter(pair, pmask, f1, o1)
-        a1 = color_jitter(img1, region, f1, o1)
-        a2 = color_jitter(img2, region, f2, o2)
-        am = asym.view(B, 1, 1, 1)
-        img1 = torch.where(am, a1, sym[:, :, :Hm])
-        img2 = torch.where(am, a2, sym[:, :, Hm:])
 
-        # ---- eraser: 1-2 boxes in image 2 filled with its mean colour (uint8 truncation)
+        # ---- eraser: 1-2 boxes in image 2
         erase = torch.rand(B, generator=gen, device=dev) < p["eraser_prob"]
         nbox = 1 + (torch.rand(B, generator=gen, device=dev) < 0.5).long()
-        mean = torch.floor(_masked_mean(img2, region))
-        emask = torch.zeros(B, 1, Hm, Wm, device=dev, dtype=torch.bool)
+        boxes = []
         for k in range(2):
             x0 = _randint(gen, torch.zeros_like(ws), ws, dev)
             y0 = _randint(gen, torch.zeros_like(hs), hs, dev)
             dx = _randint(gen, torch.full_like(ws, 50), torch.full_like(ws, 100), dev)
             dy = _randint(gen, torch.full_like(hs, 50), torch.full_like(hs, 100), dev)
-            box = ((xx >= x0.view(B, 1, 1, 1)) & (xx < (x0 + dx).view(B, 1, 1, 1)) &
-                   (yy >= y0.view(B, 1, 1, 1)) & (yy < (y0 + dy).view(B, 1, 1, 1)))
-            on = (erase & (nbox > k)).view(B, 1, 1, 1)
-            emask |= box & on
-        img2 = torch.where(emask & (region > 0), mean, img2)
+            boxes.append(torch.stack([x0, y0, dx, dy], 1))
 
         # ---- spatial parameters
         ch, cw = self.crop
@@ -241,8 +235,62 @@ class BatchAugmentor:
         x0 = _randint(gen, -mx, (rw - cw + mx).clamp_min(1 - mx), dev)
         y0 = torch.minimum(y0.clamp_min(0), (rh - ch).clamp_min(0))
         x0 = torch.minimum(x0.clamp_min(0), (rw - cw).clamp_min(0))
+        return dict(f1=f1, o1=o1, f2=f2, o2=o2, asym=asym, erase=erase, nbox=nbox, boxes=torch.stack(boxes, 1),
+                    sx=sx, sy=sy, resize=resize, rh=rh, rw=rw, hflip=hflip, vflip=vflip, x0=x0, y0=y0, sparse=sparse)
+
+    @torch.no_grad()
+    def apply(self, batch: Dict[str, torch.Tensor], params: Dict[str, torch.Tensor], mean_dtype=torch.float32,
+              sample_fp64: bool = False):
+        """The pixel work for the drawn ``params`` (see ``draw``).  ``mean_dtype`` is what the
+        contrast and eraser means are accumulated in and ``sample_fp64`` runs the bilinear warp
+        in fp64; both exist for tests and apply to the torch path only."""
+        sizes = batch["size"].to(self.device)
+        if self.native and sizes.is_cuda:
+            from ..ops._ext import use_native
+
+            if use_native(sizes):  # raises when the extension is missing
+                return self._apply_native(batch, params)
+        img1 = batch["img1"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
+        img2 = batch["img2"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
+        flow = batch["flow"].to(self.device, non_blocking=True).permute(0, 3, 1, 2).float()
+        valid = batch["valid"].to(self.device, non_blocking=True).float()
+        B, _, Hm, Wm = img1.shape
+        dev = img1.device
+        q = {k: v.to(dev) for k, v in params.items()}
+        hs, ws = sizes[:, 0], sizes[:, 1]
+        yy = torch.arange(Hm, device=dev).view(1, 1, Hm, 1)
+        xx = torch.arange(Wm, device=dev).view(1, 1, 1, Wm)
+        region = ((yy < hs.view(B, 1, 1, 1)) & (xx < ws.view(B, 1, 1, 1))).float()
+
+        # ---- photometric: asymmetric per image or symmetric on the stacked pair
+        asym, f1, o1, f2, o2 = q["asym"], q["f1"], q["o1"], q["f2"], q["o2"]
+        # symmetric: PIL sees img1 stacked over img2, so the contrast mean spans both images
+        pair = torch.cat([img1, img2], 2)
+        pmask = torch.cat([region, region], 2)
+        sym = color_jitter(pair, pmask, f1, o1, mean_dtype)
+        a1 = color_jitter(img1, region, f1, o1, mean_dtype)
+        a2 = color_jitter(img2, region, f2, o2, mean_dtype)
+        am = asym.view(B, 1, 1, 1)
+        img1 = torch.where(am, a1, sym[:, :, :Hm])
+        img2 = torch.where(am, a2, sym[:, :, Hm:])
+
+        # ---- eraser: 1-2 boxes in image 2 filled with its mean colour (uint8 truncation)
+        erase, nbox = q["erase"], q["nbox"]
+        mean = torch.floor(_masked_mean(img2, region, mean_dtype)).to(img2.dtype)
+        emask = torch.zeros(B, 1, Hm, Wm, device=dev, dtype=torch.bool)
+        for k in range(2):
+            x0, y0, dx, dy = q["boxes"][:, k].unbind(1)
+            box = ((xx >= x0.view(B, 1, 1, 1)) & (xx < (x0 + dx).view(B, 1, 1, 1)) &
+                   (yy >= y0.view(B, 1, 1, 1)) & (yy < (y0 + dy).view(B, 1, 1, 1)))
+            on = (erase & (nbox > k)).view(B, 1, 1, 1)
+            emask |= box & on
+        img2 = torch.where(emask & (region > 0), mean, img2)
 
         # ---- one warp: crop pixel -> resized (flipped) pixel -> source (cv2 half-pixel centres)
+        ch, cw = self.crop
+        hf, wf = hs.float(), ws.float()
+        sx, sy, resize, rh, rw = q["sx"], q["sy"], q["resize"], q["rh"], q["rw"]
+        hflip, vflip, x0, y0, sparse = q["hflip"], q["vflip"], q["x0"], q["y0"], q["sparse"]
         v = torch.arange(ch, device=dev).view(1, ch, 1).float()
         u = torch.arange(cw, device=dev).view(1, 1, cw).float()
         xr = (x0.view(B, 1, 1).float() + u).expand(B, ch, cw)
@@ -251,9 +299,11 @@ class BatchAugmentor:
         yr = torch.where(vflip.view(B, 1, 1), rh.view(B, 1, 1).float() - 1 - yr, yr)
         xs = ((xr + 0.5) / sx.view(B, 1, 1) - 0.5).clamp(min=0).minimum(wf.view(B, 1, 1) - 1)
         ys = ((yr + 0.5) / sy.view(B, 1, 1) - 0.5).clamp(min=0).minimum(hf.view(B, 1, 1) - 1)
-        grid = torch.stack([(2 * xs + 1) / Wm - 1, (2 * ys + 1) / Hm - 1], -1)
         src = torch.cat([img1, img2, flow], 1)
-        out = F.grid_sample(src, grid, mode="bilinear", padding_mode="border", align_corners=False)
+        if sample_fp64:
+            xs, ys, src = xs.double(), ys.double(), src.double()
+        grid = torch.stack([(2 * xs + 1) / Wm - 1, (2 * ys + 1) / Hm - 1], -1)
+        out = F.grid_sample(src, grid, mode="bilinear", padding_mode="border", align_corners=False).float()
         o1, o2, of = _q8(out[:, :3]), _q8(out[:, 3:6]), out[:, 6:8]
         of = of * torch.stack([sx, sy], 1).view(B, 2, 1, 1)
         of = of * torch.stack([torch.where(hflip, -1.0, 1.0), torch.where(vflip, -1.0, 1.0)], 1).view(B, 2, 1, 1)
@@ -263,6 +313,29 @@ class BatchAugmentor:
             sf, sv = self._sparse_flow(flow, valid, sx, sy, resize, hflip, x0, y0, rh, rw, Hm, Wm)
             sm = sparse.view(B, 1, 1, 1)
             of = torch.where(sm, sf, of)
+            dvalid = torch.where(sparse.view(B, 1, 1), sv, dvalid)
+        return o1, o2, of, dvalid
+
+    def _apply_native(self, batch, params):
+        """``apply`` through the HIP op: the uint8 batch is read once and only the crops are
+        written.  Sparse samples take their flow and valid from ``_sparse_flow`` as on the torch
+        path; whether the mixture has any is known from the specs, so nothing is read back."""
+        from ..ops.augment import augment_batch
+
+        dev = self.device
+        img1 = batch["img1"].to(dev, non_blocking=True)
+        img2 = batch["img2"].to(dev, non_blocking=True)
+        flow = batch["flow"].to(dev, non_blocking=True).float()
+        sizes = batch["size"].to(dev)
+        q = {k: v.to(dev) for k, v in params.items()}
+        o1, o2, of, dvalid = augment_batch(img1, img2, flow, sizes, q, self.crop)
+        if any(s.sparse for s in self.specs):
+            B, Hm, Wm = img1.shape[:3]
+            valid = batch["valid"].to(dev, non_blocking=True).float()
+            sf, sv = self._sparse_flow(flow.permute(0, 3, 1, 2), valid, q["sx"], q["sy"], q["resize"], q["hflip"],
+                                       q["x0"], q["y0"], q["rh"], q["rw"], Hm, Wm)
+            sparse = q["sparse"]
+            of = torch.where(sparse.view(B, 1, 1, 1), sf, of)
             dvalid = torch.where(sparse.view(B, 1, 1), sv, dvalid)
         return o1, o2, of, dvalid
 

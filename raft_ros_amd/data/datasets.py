@@ -312,7 +312,8 @@ def fetch_dataloader(args, TRAIN_DS: str = "C+T+K+S+H"):
     the reference): under DDP every rank draws the same shuffled global batch and loads its
     own slice of it (``parallel/batching.py``: uneven splits such as 10 over 8 ranks are
     exact; a rank with no sample gets an :class:`IdleLoader`), and augments with its own
-    generator (seeded by ``args.seed`` + rank) on ``args.device``."""
+    generator (seeded by ``args.seed`` + rank) on ``args.device``, through the HIP op
+    ``raft_amd::augment_batch`` when ``args.native_augment`` is set and the device is a GPU."""
     from ..parallel.batching import GlobalBatchSampler, IdleLoader, rank_batch_sizes
 
     world = int(getattr(args, "world_size", 1) or 1)
@@ -355,4 +356,5 @@ def fetch_dataloader(args, TRAIN_DS: str = "C+T+K+S+H"):
     loader = data.DataLoader(dataset, collate_fn=collate_padded, **kw)
     device = getattr(args, "device", None) or ("cuda" if torch.cuda.is_available() else "cpu")
     seed = int(getattr(args, "seed", 1234)) + 1000 * rank
-    return AugmentedLoader(loader, BatchAugmentor(specs, seed=seed, device=device))
+    native = bool(getattr(args, "native_augment", False))  # GPU: the HIP op instead of the torch ops
+    return AugmentedLoader(loader, BatchAugmentor(specs, seed=seed, device=device, native=native))

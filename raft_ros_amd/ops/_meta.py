@@ -224,6 +224,12 @@ def register() -> None:
         return (flow_fw.new_empty((B, H, W), dtype=torch.uint8), flow_fw.new_empty((B, H, W), dtype=torch.float32),
                 flow_fw.new_empty((B, 2), dtype=torch.int32))
 
+    @fake(lib + "augment_batch")
+    def _(img1, img2, flow, size, pf, pi, ch, cw):
+        B = img1.shape[0]
+        return (img1.new_empty((B, 3, ch, cw), dtype=torch.float32), img1.new_empty((B, 3, ch, cw), dtype=torch.float32),
+                img1.new_empty((B, 2, ch, cw), dtype=torch.float32), img1.new_empty((B, ch, cw), dtype=torch.float32))
+
     # mutating ops: nothing to infer
     for name in ("conv_fwd", "conv_wgrad", "conv_wgrad_params", "gru_bwd_a", "gru_bwd_b", "masked_cast",
                  "pack_flow", "apply_delta", "n2_apply", "corr_lookup_into", "corr_lookup_split_into", "convex_upsample_backward_into",

@@ -84,6 +84,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--stage synthetic: batches per rank in the device-resident pool that is replayed "
                         "(a throughput check: only pool x batch distinct pairs); 0 = 100000 distinct pairs "
                         "generated by CPU DataLoader workers (~200 pairs/s on one MI355X), globally aligned")
+    g.add_argument("--native_augment", action="store_true",
+                   help="augment each batch with the HIP op raft_amd::augment_batch (jitter, eraser and warp in "
+                        "three launches) instead of the torch ops; the same seed draws the same parameters "
+                        "(profiles/augment_bench.log)")
     g.add_argument("--profile_dir", default=None, help="capture a torch.profiler trace of steps 5-7 here")
     return p
 
