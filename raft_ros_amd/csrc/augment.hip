@@ -14,6 +14,19 @@
 //           image-2 tap inside an active eraser box reads floor(channel mean) instead.
 // Pixels outside the region are never read or written.
 //
+// Sparse ground truth (KITTI, HD1K; augment_batch_sparse, BatchAugmentor._sparse_flow is the oracle):
+// a sparse sample's flow is not interpolated.  Every region pixel with valid >= 1 is scattered to
+// its rounded position in the resized map (kept strictly inside when resized, as the reference's
+// resize_sparse_flow_map keeps 0 < x < w1), flipped horizontally and cropped; where several land
+// on one crop pixel the largest row-major source index wins, the reference's last writer.  Pass 2
+// visits every region pixel anyway and does the scatter for sparse samples: one integer atomicMax
+// of source index + 1 into the winner buffer win, which lies behind the statistics and is zeroed
+// by the same memset.  An integer maximum does not depend on the order of arrival.  (As a launch
+// of its own the scatter was 3 % slower on the Sintel-stage mixture and 3 % faster on the KITTI
+// stage, profiles/augment_bench.log: the launch count stays three.)  Pass 3 then
+// skips a sparse sample's flow taps, reads its four winners and gathers their flow; the images of
+// a sparse sample are computed like any other.  The dense op instantiates neither.
+//
 // Sums are integers: the luma of integer-valued channels is 0 or at least 0.114 and below 256, so
 // luma * 2^27 is an exact integer below 2^35, and up to 2^27 of them fit a 64-bit sum.  Integer
 // atomics are associative: the statistics, and with them the outputs, do not depend on the order
@@ -149,8 +162,49 @@ __device__ __forceinline__ void block_atomic_sum(long long (&v)[N], long long* d
   }
 }
 
-// passes 1 and 2: grid (blocks, B), a block strides over the in-region pixels of its sample
-template <bool FULL>
+// what the scatter of a sparse sample needs of its drawn parameters
+struct SparseMap {
+  float sx, sy;
+  int resize, hflip, rh, rw, x0, y0;
+};
+
+__device__ __forceinline__ SparseMap sparse_map(const AugmentArgs& a, int b) {
+  const float* pf = a.pf + (long)b * kAugPF;
+  const int* pi = a.pi + (long)b * kAugPI;
+  SparseMap m;
+  m.sx = pf[kAugSx];
+  m.sy = pf[kAugSy];
+  m.resize = (a.flags[b] & kAugResize) != 0;
+  m.hflip = pi[kAugHflip] != 0;
+  m.rh = pi[kAugRh];
+  m.rw = pi[kAugRw];
+  m.x0 = pi[kAugX0];
+  m.y0 = pi[kAugY0];
+  return m;
+}
+
+// Region pixel (x, y) at padded offset off of sparse sample b -> its crop pixel, if it has one:
+// win = max(win, source index + 1).
+__device__ __forceinline__ void scatter_pixel(const AugmentArgs& a, int b, const SparseMap& m, int x, int y, long off) {
+  if (!(a.valid[off] >= 1.f)) return;  // a NaN is not valid
+  long xn = x, yn = y;
+  if (m.resize) {
+    const float xf = rintf((float)x * m.sx), yf = rintf((float)y * m.sy);  // half to even, like torch.round
+    if (!(xf > 0.f && yf > 0.f && xf < 2147483648.f && yf < 2147483648.f)) return;  // or a NaN
+    xn = (long)xf;
+    yn = (long)yf;
+    if (xn >= m.rw || yn >= m.rh) return;
+  }
+  if (m.hflip) xn = (long)m.rw - 1 - xn;
+  const long cx = xn - m.x0, cy = yn - m.y0;
+  if (cx < 0 || cx >= a.cw || cy < 0 || cy >= a.ch) return;
+  // inside (B, ch, cw); y * Wm + x + 1 <= Hm * Wm <= 2^26
+  atomicMax(a.win + ((long)b * a.ch + cy) * a.cw + cx, y * a.Wm + x + 1);
+}
+
+// passes 1 and 2: grid (blocks, B), a block strides over the in-region pixels of its sample.
+// SCATTER (pass 2 of augment_batch_sparse): the sparse samples' valid pixels are scattered too.
+template <bool FULL, bool SCATTER = false>
 __global__ __launch_bounds__(256) void augment_jitter_kernel(AugmentArgs a) {
   const int b = blockIdx.y;
   const int h = clampi(a.size[2 * b], 0, a.Hm), w = clampi(a.size[2 * b + 1], 0, a.Wm);
@@ -176,9 +230,18 @@ __global__ __launch_bounds__(256) void augment_jitter_kernel(AugmentArgs a) {
   }
   long long acc[3] = {0, 0, 0};
   const long base = (long)b * a.Hm * a.Wm;
+  bool sp = false;
+  SparseMap sm{};
+  if constexpr (SCATTER) {
+    sp = (a.flags[b] & kAugSparse) != 0;
+    if (sp) sm = sparse_map(a, b);
+  }
   for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
     const int y = p / w, x = p - y * w;
     const long off = base + (long)y * a.Wm + x;  // in-region pixel: off < B * Hm * Wm
+    if constexpr (SCATTER) {
+      if (sp) scatter_pixel(a, b, sm, x, y, off);
+    }
     const Rgb c1 = jitter_pixel<FULL>(load_rgb(a.img1 + 3 * off), f1, o1, m1);
     const Rgb c2 = jitter_pixel<FULL>(load_rgb(a.img2 + 3 * off), f2, o2, m2);
     if (FULL) {
@@ -227,8 +290,9 @@ __device__ __forceinline__ float blend(float nw, float ne, float sw, float se, f
   return ((nw * wnw + ne * wne) + sw * wsw) + se * wse;
 }
 
-// pass 3: grid (blocks, B), a thread writes 4 consecutive pixels of one crop row
-template <bool VEC>
+// pass 3: grid (blocks, B), a thread writes 4 consecutive pixels of one crop row.  SPARSE
+// (augment_batch_sparse): a sparse sample's flow and valid come from its winners, not from taps.
+template <bool VEC, bool SPARSE = false>
 __global__ __launch_bounds__(256) void augment_warp_kernel(AugmentArgs a) {
   const int b = blockIdx.y;
   const int G = (a.cw + 3) >> 2;
@@ -264,6 +328,35 @@ __global__ __launch_bounds__(256) void augment_warp_kernel(AugmentArgs a) {
     const long base = (long)b * a.Hm * a.Wm;
     const long row0 = base + (long)ty.i0 * a.Wm, row1 = base + (long)ty.i1 * a.Wm;
     const float fu = hflip ? -1.f : 1.f, fv = vflip ? -1.f : 1.f;
+    bool sp = false;
+    if constexpr (SPARSE) sp = (a.flags[b] & kAugSparse) != 0;
+    if constexpr (SPARSE) {
+      if (sp) {
+        const int* wp = a.win + (long)b * a.ch * a.cw + (long)y * a.cw + xg;
+        int wv[4] = {0, 0, 0, 0};
+        if constexpr (VEC) {  // cw % 4 == 0: the group is 16-byte aligned
+          const int4 v4 = *reinterpret_cast<const int4*>(wp);
+          wv[0] = v4.x;
+          wv[1] = v4.y;
+          wv[2] = v4.z;
+          wv[3] = v4.w;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (j < n) wv[j] = wp[j];
+        }
+        const bool rs = (a.flags[b] & kAugResize) != 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (wv[j] > 0) {  // the winner's source index + 1: a region pixel of this sample
+            const float2 f = *reinterpret_cast<const float2*>(a.flow + 2 * (base + (wv[j] - 1)));
+            o[6][j] = (rs ? f.x * sx : f.x) * fu;
+            o[7][j] = rs ? f.y * sy : f.y;  // no vertical flip for sparse samples
+            o[8][j] = 1.f;
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j < n) {
@@ -277,7 +370,7 @@ __global__ __launch_bounds__(256) void augment_warp_kernel(AugmentArgs a) {
         for (int k = 0; k < 4; ++k) {
           c1[k] = a.jit1[q[k]];
           c2[k] = a.jit2[q[k]];
-          fl[k] = *reinterpret_cast<const float2*>(a.flow + 2 * q[k]);
+          fl[k] = sp ? make_float2(0.f, 0.f) : *reinterpret_cast<const float2*>(a.flow + 2 * q[k]);
           bool er = false;
 #pragma unroll
           for (int e = 0; e < 2; ++e)
@@ -292,11 +385,13 @@ __global__ __launch_bounds__(256) void augment_warp_kernel(AugmentArgs a) {
           o[3 + c][j] = q8(blend((float)(c2[0] >> sh & 255u), (float)(c2[1] >> sh & 255u), (float)(c2[2] >> sh & 255u),
                                  (float)(c2[3] >> sh & 255u), wnw, wne, wsw, wse));
         }
-        const float u = blend(fl[0].x, fl[1].x, fl[2].x, fl[3].x, wnw, wne, wsw, wse) * sx * fu;
-        const float v = blend(fl[0].y, fl[1].y, fl[2].y, fl[3].y, wnw, wne, wsw, wse) * sy * fv;
-        o[6][j] = u;
-        o[7][j] = v;
-        o[8][j] = fabsf(u) < 1000.f && fabsf(v) < 1000.f ? 1.f : 0.f;
+        if (!sp) {
+          const float u = blend(fl[0].x, fl[1].x, fl[2].x, fl[3].x, wnw, wne, wsw, wse) * sx * fu;
+          const float v = blend(fl[0].y, fl[1].y, fl[2].y, fl[3].y, wnw, wne, wsw, wse) * sy * fv;
+          o[6][j] = u;
+          o[7][j] = v;
+          o[8][j] = fabsf(u) < 1000.f && fabsf(v) < 1000.f ? 1.f : 0.f;
+        }
       }
     }
   }
@@ -335,18 +430,37 @@ hipError_t launch_augment_batch(const AugmentArgs& a, hipStream_t s) {
       (reinterpret_cast<uintptr_t>(a.out2) & 15) || (reinterpret_cast<uintptr_t>(a.oflow) & 15) ||
       (reinterpret_cast<uintptr_t>(a.ovalid) & 15))
     return hipErrorInvalidValue;
-  RAFT_HIP_CHECK(hipMemsetAsync(a.stats, 0, (size_t)a.B * kAugStats * sizeof(long long), s));
+  // sparse ground truth: all three pointers or none; win directly behind stats, so that the one
+  // memset zeroes both
+  const bool sparse = a.valid != nullptr || a.flags != nullptr || a.win != nullptr;
+  size_t zero = (size_t)a.B * kAugStats * sizeof(long long);
+  if (sparse) {
+    if (a.valid == nullptr || a.flags == nullptr || a.win != reinterpret_cast<int*>(a.stats + (long)a.B * kAugStats) ||
+        (reinterpret_cast<uintptr_t>(a.win) & 15))
+      return hipErrorInvalidValue;
+    zero += (size_t)a.B * a.ch * a.cw * sizeof(int);
+  }
+  RAFT_HIP_CHECK(hipMemsetAsync(a.stats, 0, zero, s));
   if (HW > 0) {
     const dim3 grid((unsigned)(HW + 255) / 256 < 1024u ? (unsigned)(HW + 255) / 256 : 1024u, (unsigned)a.B);
     hipLaunchKernelGGL(augment_jitter_kernel<false>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(augment_jitter_kernel<true>, grid, dim3(256), 0, s, a);
+    if (sparse)
+      hipLaunchKernelGGL((augment_jitter_kernel<true, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(augment_jitter_kernel<true>, grid, dim3(256), 0, s, a);
   }
   const long groups = (long)a.ch * ((a.cw + 3) >> 2);
   const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)a.B);
-  if (a.cw % 4 == 0)
+  if (sparse) {
+    if (a.cw % 4 == 0)
+      hipLaunchKernelGGL((augment_warp_kernel<true, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((augment_warp_kernel<false, true>), grid, dim3(256), 0, s, a);
+  } else if (a.cw % 4 == 0) {
     hipLaunchKernelGGL(augment_warp_kernel<true>, grid, dim3(256), 0, s, a);
-  else
+  } else {
     hipLaunchKernelGGL(augment_warp_kernel<false>, grid, dim3(256), 0, s, a);
+  }
   return hipGetLastError();
 }
 

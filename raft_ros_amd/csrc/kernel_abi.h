@@ -687,6 +687,8 @@ constexpr int kAugX0 = 22;    // pi: crop origin in the resized (flipped) image
 constexpr int kAugY0 = 23;
 constexpr int kAugPI = 24;    // ints per sample
 constexpr int kAugStats = 8;  // 64-bit words of statistics per sample (5 used)
+constexpr int kAugSparse = 1;  // flags: flow and valid are the sparse scatter (KITTI, HD1K), not the bilinear warp
+constexpr int kAugResize = 2;  // flags: the sample is resized (a sparse sample's inside rule and flow scale)
 
 struct AugmentArgs {
   const unsigned char* img1;  // (B, Hm, Wm, 3) uint8, zero padded
@@ -703,6 +705,12 @@ struct AugmentArgs {
   float* oflow;               // (B, 2, ch, cw)
   float* ovalid;              // (B, ch, cw)
   int B, Hm, Wm, ch, cw;
+  // Sparse ground truth (augment_batch_sparse); all three null for the dense op.
+  const float* valid;         // (B, Hm, Wm) fp32: a source pixel counts where valid >= 1
+  const int* flags;           // (B) per sample: kAugSparse | kAugResize
+  int* win;                   // (B, ch, cw) workspace: 1 + the largest source index y * Wm + x that lands on
+                              //   a crop pixel, 0 = none; 16-byte aligned, directly behind stats and zeroed
+                              //   with it by the one memset
 };
 
 // ============================================================================ correlation build

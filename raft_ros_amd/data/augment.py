@@ -4,8 +4,9 @@ The reference augments one sample at a time on the CPU, inside DataLoader
 workers, with OpenCV and torchvision (core/utils/augmentor.py:15-246).  Here
 the workers only decode files; a whole padded batch is augmented on the GPU
 (or on the CPU for tests / single samples) with tensor ops, or on the GPU with
-``BatchAugmentor(native=True)`` by the HIP op ``raft_amd::augment_batch``
-(csrc/augment.hip, ops/augment.py) that computes the same:
+``BatchAugmentor(native=True)`` by the HIP ops ``raft_amd::augment_batch`` and, for mixtures
+with sparse datasets, ``raft_amd::augment_batch_sparse`` (csrc/augment.hip, ops/augment.py) that
+compute the same:
 
 * photometric: ColorJitter with the PIL semantics of torchvision (random order
   of brightness / contrast / saturation / hue, each result rounded to uint8),
@@ -318,8 +319,9 @@ class BatchAugmentor:
 
     def _apply_native(self, batch, params):
         """``apply`` through the HIP op: the uint8 batch is read once and only the crops are
-        written.  Sparse samples take their flow and valid from ``_sparse_flow`` as on the torch
-        path; whether the mixture has any is known from the specs, so nothing is read back."""
+        written.  Whether the mixture has sparse samples is known from the specs, so nothing is
+        read back: with any, ``valid`` goes to the op too and a sparse sample's flow and valid are
+        scattered inside it (what ``_sparse_flow`` computes on the torch path)."""
         from ..ops.augment import augment_batch
 
         dev = self.device
@@ -328,16 +330,10 @@ class BatchAugmentor:
         flow = batch["flow"].to(dev, non_blocking=True).float()
         sizes = batch["size"].to(dev)
         q = {k: v.to(dev) for k, v in params.items()}
-        o1, o2, of, dvalid = augment_batch(img1, img2, flow, sizes, q, self.crop)
+        valid = None
         if any(s.sparse for s in self.specs):
-            B, Hm, Wm = img1.shape[:3]
             valid = batch["valid"].to(dev, non_blocking=True).float()
-            sf, sv = self._sparse_flow(flow.permute(0, 3, 1, 2), valid, q["sx"], q["sy"], q["resize"], q["hflip"],
-                                       q["x0"], q["y0"], q["rh"], q["rw"], Hm, Wm)
-            sparse = q["sparse"]
-            of = torch.where(sparse.view(B, 1, 1, 1), sf, of)
-            dvalid = torch.where(sparse.view(B, 1, 1), sv, dvalid)
-        return o1, o2, of, dvalid
+        return augment_batch(img1, img2, flow, sizes, q, self.crop, valid=valid)
 
     def _sparse_flow(self, flow, valid, sx, sy, resize, hflip, x0, y0, rh, rw, Hm, Wm):
         """Reference ``resize_sparse_flow_map`` + flip + crop: every valid source sample is

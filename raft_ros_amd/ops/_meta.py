@@ -230,6 +230,12 @@ def register() -> None:
         return (img1.new_empty((B, 3, ch, cw), dtype=torch.float32), img1.new_empty((B, 3, ch, cw), dtype=torch.float32),
                 img1.new_empty((B, 2, ch, cw), dtype=torch.float32), img1.new_empty((B, ch, cw), dtype=torch.float32))
 
+    @fake(lib + "augment_batch_sparse")
+    def _(img1, img2, flow, valid, size, pf, pi, flags, ch, cw):
+        B = img1.shape[0]
+        return (img1.new_empty((B, 3, ch, cw), dtype=torch.float32), img1.new_empty((B, 3, ch, cw), dtype=torch.float32),
+                img1.new_empty((B, 2, ch, cw), dtype=torch.float32), img1.new_empty((B, ch, cw), dtype=torch.float32))
+
     # mutating ops: nothing to infer
     for name in ("conv_fwd", "conv_wgrad", "conv_wgrad_params", "gru_bwd_a", "gru_bwd_b", "masked_cast",
                  "pack_flow", "apply_delta", "n2_apply", "corr_lookup_into", "corr_lookup_split_into", "convex_upsample_backward_into",
