@@ -1315,6 +1315,8 @@ void gru_bwd_b(const at::Tensor& drh, const at::Tensor& r, const at::Tensor& h, 
   pm_any(h, "h", P, at::kBFloat16);
   pm_any(carry, "carry", P, at::kFloat);
   pm_any(dr, "dr", P, at::kBFloat16);
+  TORCH_CHECK(r.size(1) >= C && h.size(1) >= C && carry.size(1) >= C && dr.size(1) >= C,
+              "raft_amd gru_bwd_b: channel mismatch");
   const c10::DeviceGuard guard(drh.device());
   HIP_OK(launch_gru_bwd_b(drh.data_ptr<float>(), drh.stride(0), r.data_ptr(), r.stride(0), h.data_ptr(),
                           h.stride(0), carry.data_ptr<float>(), carry.stride(0), dr.data_ptr(), dr.stride(0), P,

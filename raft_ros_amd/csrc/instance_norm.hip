@@ -6,9 +6,12 @@
 // channels-last activation is copied to NCHW and back around every norm (forward
 // and backward) -- ~70 full-resolution copies per training step.  These kernels
 // work on the NHWC layout directly:
-//   stats:  per (n, c) sum / sum of squares, 16-byte loads of 8 channels per
-//           thread, fixed-order LDS reduction to one partial per 1024-pixel chunk,
-//           then a fixed-order sum of the partials (deterministic, no atomics);
+//   stats:  per (n, c) and 1024-pixel chunk the sums of (x - pivot) and (x - pivot)^2
+//           about the chunk's first pixel, 16-byte loads of 8 channels per thread,
+//           fixed-order LDS reduction to one (mean, M2) partial per chunk, then a
+//           fixed-order Chan combination of the partials (deterministic, no atomics;
+//           no E[x^2] - E[x]^2 cancellation when |mean| >> std, and a constant
+//           channel has variance exactly 0);
 //   apply:  y = relu?((x - mean) * rstd), vectorised;
 //   bwd:    dxhat = dy * [xhat > 0 if relu]; per (n, c) sums of dxhat and
 //           dxhat*xhat; dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat*xhat)).
@@ -60,7 +63,7 @@ struct Vec8IO<float> {
 constexpr int PIX_PER_BLOCK = 1024;
 
 // Per-(image, channel) partial sums over one PIX_PER_BLOCK pixel chunk.
-// mode 0: sums of x and x^2.  mode 1: sums of dxhat and dxhat*xhat (needs stats + dy).
+// mode 0: (mean, M2) of x.  mode 1: sums of dxhat and dxhat*xhat (needs stats + dy).
 // Every block writes its own partial (no atomics, no memset): the reduction order is
 // fixed, so the statistics are bit-reproducible run to run and graph replays need no
 // zero-initialised accumulator.
@@ -74,6 +77,9 @@ __global__ __launch_bounds__(256) void in_partial_kernel(const T* __restrict__ x
   const int R = 256 / G;
   const int tid = threadIdx.x;
   const int cg = tid % G, pr = tid / G;
+  const int p0 = blockIdx.x * PIX_PER_BLOCK;
+  const int p1 = min(p0 + PIX_PER_BLOCK, HW);
+  const long piv_off = ((long)n * HW + p0) * C;  // the chunk's first pixel: the pivot of its channels
   float a1[8], a2[8], mean[8], rstd[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -85,8 +91,7 @@ __global__ __launch_bounds__(256) void in_partial_kernel(const T* __restrict__ x
     }
   }
   if (pr < R) {
-    const int p0 = blockIdx.x * PIX_PER_BLOCK;
-    const int p1 = min(p0 + PIX_PER_BLOCK, HW);
+    if (MODE == 0) Vec8IO<T>::load(x + piv_off + cg * 8, mean);
     for (int p = p0 + pr; p < p1; p += R) {
       const long off = ((long)n * HW + p) * C + cg * 8;
       float v[8];
@@ -94,8 +99,9 @@ __global__ __launch_bounds__(256) void in_partial_kernel(const T* __restrict__ x
       if (MODE == 0) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          a1[j] += v[j];
-          a2[j] += v[j] * v[j];
+          const float d = v[j] - mean[j];
+          a1[j] += d;
+          a2[j] += d * d;
         }
       } else {
         float g[8];
@@ -123,27 +129,44 @@ __global__ __launch_bounds__(256) void in_partial_kernel(const T* __restrict__ x
       s2 += r2[r * C + c];
     }
     const long o = (((long)blockIdx.x * N + n) * C + c) * 2;
-    part[o] = s1;
-    part[o + 1] = s2;
+    if (MODE == 0) {
+      // s1, s2 are sums of (x - pivot): the pivot is a sample of the channel, so it lies within a
+      // few standard deviations of the chunk mean and s2 - s1^2 / cnt loses nothing to the offset
+      const float cnt = (float)(p1 - p0), ms = s1 / cnt;
+      part[o] = to_f32(x[piv_off + c]) + ms;
+      part[o + 1] = fmaxf(s2 - s1 * ms, 0.f);
+    } else {
+      part[o] = s1;
+      part[o + 1] = s2;
+    }
   }
 }
 
-// Sum the per-chunk partials in a fixed order.  mode 0 -> (mean, rstd); mode 1 -> raw sums.
+// Combine the per-chunk partials in a fixed order.  mode 0 -> (mean, rstd); mode 1 -> raw sums.
 __global__ void in_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int chunks, long NC,
                                  int HW, float eps, int mode) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= NC) return;
-  float s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < chunks; ++k) {
-    s1 += part[(k * NC + i) * 2];
-    s2 += part[(k * NC + i) * 2 + 1];
-  }
   if (mode == 0) {
-    const float m = s1 / HW;
-    const float var = fmaxf(s2 / HW - m * m, 0.f);
-    out[2 * i] = m;
-    out[2 * i + 1] = rsqrtf(var + eps);
+    // Chan-combine the chunks' (mean, M2) in chunk order: no E[x^2] - E[x]^2 cancellation
+    float cn = 0.f, cm = 0.f, cM2 = 0.f;
+    for (int k = 0; k < chunks; ++k) {
+      const float nb = (float)min(PIX_PER_BLOCK, HW - k * PIX_PER_BLOCK);
+      const float mb = part[(k * NC + i) * 2], M2b = part[(k * NC + i) * 2 + 1];
+      const float nn = cn + nb, d = mb - cm;
+      const float f = nb / nn;  // 1 for the first chunk: its mean is taken over exactly
+      cm += d * f;
+      cM2 += M2b + d * d * cn * f;
+      cn = nn;
+    }
+    out[2 * i] = cm;
+    out[2 * i + 1] = rsqrtf(cM2 / HW + eps);
   } else {
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = 0; k < chunks; ++k) {
+      s1 += part[(k * NC + i) * 2];
+      s2 += part[(k * NC + i) * 2 + 1];
+    }
     out[2 * i] = s1;
     out[2 * i + 1] = s2;
   }
