@@ -4,7 +4,9 @@
     python evaluate.py --model=models/raft-things.pth --dataset=sintel --mixed_precision
 
 Extra: ``--dataset synthetic`` (generated pairs with exact ground truth),
-``--submission {sintel,kitti}`` (+ ``--warm_start``), ``--device``, ``--iters``.
+``--submission {sintel,kitti}`` (+ ``--warm_start``), ``--device``, ``--iters``,
+``--device_metrics`` (the metrics stay on the device until the dataset is finished:
+raft_ros_amd/ops/metrics.py) and ``--val_workers N`` (decode samples in N DataLoader workers).
 Checkpoints load with or without the ``module.`` prefix, on any device.
 """
 from __future__ import annotations
@@ -45,6 +47,9 @@ def main(argv=None):
     p.add_argument("--submission", choices=["sintel", "kitti"], default=None)
     p.add_argument("--warm_start", action="store_true")
     p.add_argument("--dataset_root", default=None)
+    p.add_argument("--device_metrics", action="store_true",
+                   help="compute EPE and the px rates on the model's device (HIP op on a GPU), one read-back per dataset")
+    p.add_argument("--val_workers", type=int, default=0, help="DataLoader workers that decode the validation samples")
     args = p.parse_args(argv)
     if args.dataset_root:
         os.environ["RAFT_DATASET_ROOT"] = args.dataset_root
@@ -54,12 +59,15 @@ def main(argv=None):
         checkpoint.load_weights(model, args.model)
     model.to(args.device).eval()
     kw = {} if args.iters is None else {"iters": args.iters}
+    sub_kw = dict(kw)
+    if args.device_metrics or args.val_workers:
+        kw.update(device_metrics=args.device_metrics, workers=args.val_workers)
 
     with torch.inference_mode():
         if args.submission == "sintel":
-            return create_sintel_submission(model, warm_start=args.warm_start, **kw)
+            return create_sintel_submission(model, warm_start=args.warm_start, **sub_kw)
         if args.submission == "kitti":
-            return create_kitti_submission(model, **kw)
+            return create_kitti_submission(model, **sub_kw)
         if args.dataset == "chairs":
             return validate_chairs(model, **kw)
         if args.dataset == "sintel":

@@ -666,6 +666,26 @@ struct FbConsistencyArgs {
   long HW;  // H * W
 };
 
+// Validation metrics of a padded prediction against ground truth (csrc/flow_metrics.hip): the
+// end-point error summed in float64 and the threshold counts, per image.  A thread takes 4
+// consecutive pixels of one row, a block 256 such groups; every block leaves one partial.
+constexpr int kMetricCounts = 5;  // counted pixels, epe < 1, epe < 3, epe < 5, KITTI outliers
+RAFT_HD inline long flow_metrics_row_groups(long W) { return (W + 3) / 4; }
+// blocks (= partials) per image; 0 for an empty image
+RAFT_HD inline long flow_metrics_blocks(long H, long W) { return (H * flow_metrics_row_groups(W) + 255) / 256; }
+
+struct FlowMetricsArgs {
+  const float* pr;     // (B, 2, Hp, Wp) fp32 padded prediction, read at [top, top + H) x [left, left + W)
+  const float* gt;     // (B, 2, H, W) fp32 ground truth
+  const float* valid;  // (B, H, W) fp32 or null: a pixel counts where valid >= 0.5
+  double* part_sum;    // [B][nblk] scratch: a block's sum of epe over its counted pixels
+  int* part_cnt;       // [B][nblk][kMetricCounts] scratch: a block's counts
+  double* epe_sum;     // [B]
+  int* counts;         // [B][kMetricCounts]
+  int B, H, W, Hp, Wp, top, left;
+  int nblk;  // flow_metrics_blocks(H, W)
+};
+
 // Training augmentation of a padded batch (csrc/augment.hip): colour jitter, eraser and the
 // resize / flip / crop warp of data/augment.py.  The drawn parameters of sample b are the rows
 // pf[b] (fp32) and pi[b] (int32), laid out by the offsets below (ops/augment.py packs them).
@@ -755,6 +775,8 @@ hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
 hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
 // fb_consistency.hip
 hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
+// flow_metrics.hip
+hipError_t launch_flow_metrics(const FlowMetricsArgs& a, hipStream_t s);
 // augment.hip
 hipError_t launch_augment_batch(const AugmentArgs& a, hipStream_t s);
 // conv_igemm.hip

@@ -224,6 +224,11 @@ def register() -> None:
         return (flow_fw.new_empty((B, H, W), dtype=torch.uint8), flow_fw.new_empty((B, H, W), dtype=torch.float32),
                 flow_fw.new_empty((B, 2), dtype=torch.int32))
 
+    @fake(lib + "flow_metrics")
+    def _(flow_pr, flow_gt, valid, top, left):
+        B = flow_gt.shape[0]
+        return flow_pr.new_empty((B,), dtype=torch.float64), flow_pr.new_empty((B, 5), dtype=torch.int32)
+
     @fake(lib + "augment_batch")
     def _(img1, img2, flow, size, pf, pi, ch, cw):
         B = img1.shape[0]

@@ -173,7 +173,8 @@ def train(args: Namespace, on_finish=None) -> str:
             # BatchNorm running statistics: take rank 0's (the reference's replica-0 statistics,
             # train.py:138), which also covers ranks that sat idle and never updated theirs
             ddp.broadcast_buffers(model, info)
-            results = run_validation(model, args.validation, rank=info.rank, world=info.world_size)
+            results = run_validation(model, args.validation, rank=info.rank, world=info.world_size,
+                                     device_metrics=getattr(args, "device_metrics", False))
             logger.write_dict(results)
             model.train()
             if args.stage != "chairs":

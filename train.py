@@ -65,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "parallel/grad_sync.py) or torch DistributedDataParallel (ddp)")
     g.add_argument("--bucket_mb", type=float, default=10.0,
                    help="DDP gradient bucket size (--dp_impl ddp)")
+    g.add_argument("--device_metrics", action="store_true",
+                   help="validation metrics on the device (HIP op raft_amd::flow_metrics): one read-back per "
+                        "dataset instead of several per sample")
     g.add_argument("--seed", type=int, default=1234)
     g.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible steps: torch.use_deterministic_algorithms + the native kernels' "
