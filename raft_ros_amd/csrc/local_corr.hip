@@ -81,9 +81,12 @@ __global__ __launch_bounds__(256) void local_corr_fwd_kernel(const T* __restrict
     const long p = pix - b * HW1;
     const float cx = coords[(long)b * 2 * HW1 + p], cy = coords[(long)b * 2 * HW1 + HW1 + p];
     const bool ok = isfinite(cx) && isfinite(cy);
-    const float x0f = floorf(clampf(cx)), y0f = floorf(clampf(cy));
-    fx = cx - x0f;
-    fy = cy - y0f;
+    // the fraction of the clamped coordinate, 0 for a non-finite query: every dot is 0 there, and
+    // 0 * (a NaN, infinite or overflowing weight product) would be NaN instead of the zero padding
+    const float cxc = ok ? clampf(cx) : 0.f, cyc = ok ? clampf(cy) : 0.f;
+    const float x0f = floorf(cxc), y0f = floorf(cyc);
+    fx = cxc - x0f;
+    fy = cyc - y0f;
     const T* a = f1 + pix * C;
     for (int n = lane; n < nb * nb; n += 64) {
       const int yy = (int)y0f - r + n / nb, xx = (int)x0f - r + n % nb;
