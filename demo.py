@@ -13,7 +13,10 @@ here the visualisation is shown with cv2 when it is importable and a display is
 available, and is always written to ``--output`` (default ``demo-output/``) as
 PNG.  With ``--occlusion`` every pair also runs backwards (one batch of two) and the
 forward-backward consistency mask is written beside the flow as ``occ_%04d.png``
-(0 consistent, 128 inconsistent, 255 the flow leaves the frame).  ``--model`` is
+(0 consistent, 128 inconsistent, 255 the flow leaves the frame).  With ``--tracks`` a
+grid of points (one per ``--track_cell`` cell of the image) is followed through the
+flows on the device and the tracked points of every pair are written to
+``tracks.csv`` (``frame,id,x,y,prev_x,prev_y,age``, image coordinates).  ``--model`` is
 optional (random weights) so the pipeline can be smoke-tested without the
 pretrained files.
 """
@@ -33,6 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from raft_ros_amd.models import RAFT  # noqa: E402
 from raft_ros_amd.ops.consistency import OCC_LEVELS, fb_consistency  # noqa: E402
 from raft_ros_amd.ops.frame_io import flow_to_image, ingest_frames  # noqa: E402
+from raft_ros_amd.ops.track import PointTracker  # noqa: E402
 from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
 from raft_ros_amd.utils.utils import InputPadder  # noqa: E402
@@ -110,6 +114,10 @@ def demo(args):
     flow_prev = None  # --warm_start: the last pair's low-resolution flow, projected onto its second frame
     device_viz = getattr(args, "device_viz", False)
     occlusion = getattr(args, "occlusion", False)
+    # --tracks: consecutive pairs of the sorted directory are continuous; the tracker itself
+    # starts over when the frame size changes
+    tracker = PointTracker(S=getattr(args, "track_cell", 32)) if getattr(args, "tracks", False) else None
+    rows = ["frame,id,x,y,prev_x,prev_y,age"]
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
             if device_viz:
@@ -123,6 +131,7 @@ def demo(args):
                 image1, image2 = padder.pad(image1, image2)
             if flow_prev is not None and flow_prev.shape[-2:] != (image1.shape[-2] // 8, image1.shape[-1] // 8):
                 flow_prev = None  # the frame size changed: cold start
+            flow_bw = None
             if occlusion:
                 # both directions as one batch of the pair and the swapped pair; the backward
                 # direction has no previous flow and always starts cold
@@ -130,6 +139,7 @@ def demo(args):
                 flow_low, flow_up = model(torch.cat([image1, image2]), torch.cat([image2, image1]), iters=args.iters,
                                           flow_init=init, test_mode=True)
                 occ = fb_consistency(flow_up[0:1], flow_up[1:2])[0]
+                flow_bw = flow_up[1:2].float().contiguous()
                 flow_low, flow_up = flow_low[0:1], flow_up[0:1]
                 if rank == 0:  # mono mask: 0 consistent, 128 inconsistent, 255 the flow leaves the frame
                     mask = OCC_LEVELS[occ[0].cpu().numpy()]
@@ -138,10 +148,23 @@ def demo(args):
                 flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
             if warm:
                 flow_prev = forward_splat_nearest(flow_low)
+            if tracker is not None:
+                # the points live in the unpadded image inside the padded frame; with --occlusion
+                # the forward-backward check drops inconsistent points
+                left, top = padder._pad[0], padder._pad[2]
+                roi = (left, top, padder.wd, padder.ht)
+                pos, prv, ids, age, _, status, _, _ = tracker.update(flow_up.float().contiguous(), flow_bw, roi=roi)
+                pos, prv, ids, age, status = [t[0].cpu().numpy() for t in (pos, prv, ids, age, status)]
+                for j in np.flatnonzero(status == 0):
+                    rows.append("%d,%d,%.3f,%.3f,%.3f,%.3f,%d" % (k, ids[j], pos[j, 0] - left, pos[j, 1] - top,
+                                                                 prv[j, 0] - left, prv[j, 1] - top, age[j]))
             out = os.path.join(args.output, "flow_%04d.png" % k)
             if rank == 0:
                 viz(image1, flow_up, out, show=args.show, device_viz=device_viz)
             outs.append(out)
+    if tracker is not None and rank == 0:
+        with open(os.path.join(args.output, "tracks.csv"), "w") as f:
+            f.write("\n".join(rows) + "\n")
     return outs
 
 
@@ -170,6 +193,10 @@ def main(argv=None):
                    help="run every pair in both directions (one batch of two) and write the forward-backward "
                         "consistency mask as occ_%%04d.png beside the flow: 0 consistent, 128 inconsistent, "
                         "255 the flow leaves the frame (ops/consistency.py)")
+    p.add_argument("--tracks", action="store_true",
+                   help="follow a grid of points through the flows on the device and write the tracked points of "
+                        "every pair to tracks.csv (frame,id,x,y,prev_x,prev_y,age; ops/track.py)")
+    p.add_argument("--track_cell", type=int, default=32, help="with --tracks: the cell size, one point per cell")
     p.add_argument("--query_shard", action="store_true",
                    help="under torchrun: shard the correlation volume over the ranks' query pixels "
                         "(high-resolution inference; raft_ros_amd/parallel/query_shard.py)")

@@ -666,6 +666,34 @@ struct FbConsistencyArgs {
   long HW;  // H * W
 };
 
+// Point tracks (csrc/track_points.hip): a grid of points, one per cell of the roi, advanced by
+// one pair's flow; untrusted points dropped, crowded cells thinned, empty cells re-seeded.
+// N = Gy * Gx is the number of cells and of slots per image.
+struct TrackPointsArgs {
+  const float* pos;       // (B, N, 2) fp32 (x, y) in frame coordinates
+  const long long* ids;   // (B, N), all >= 0
+  const int* age;         // (B, N), all >= 0
+  const long long* epoch; // (1)
+  const float* fw;        // (B, 2, H, W) fp32 forward flow
+  const float* bw;        // (B, 2, H, W) fp32 backward flow, or null: only the frame test applies
+  float* pos_out;         // (B, N, 2); phase 1 leaves the target q of every slot here
+  float* prev;            // (B, N, 2): the position on entry, (NaN, NaN) for a re-seeded slot
+  long long* ids_out;     // (B, N)
+  int* age_out;           // (B, N)
+  long long* epoch_out;   // (1) epoch + 1
+  unsigned char* status;  // (B, N) 0 tracked, 1 inconsistent, 2 left the roi, 3 crowded out
+  float* err2;            // (B, N) squared forward-backward error, +inf for status 2
+  int* counts;            // (B, 4) slots per status
+  unsigned long long* keys;  // (B, N) workspace, set to all ones per call: the claim of each cell,
+                             //   (0xffffffff - age) << 32 | slot of the oldest claimant
+  int* free_cells;        // (B, N) workspace: the unowned cells of an image in cell order
+  float alpha1, alpha2;
+  int B, N, H, W;
+  int left, top, w, h;    // roi inside the frame
+  int S, Gx, Gy;          // cell size and grid: Gx = ceil(w / S), Gy = ceil(h / S), N = Gy * Gx
+  long HW;                // H * W
+};
+
 // Validation metrics of a padded prediction against ground truth (csrc/flow_metrics.hip): the
 // end-point error summed in float64 and the threshold counts, per image.  A thread takes 4
 // consecutive pixels of one row, a block 256 such groups; every block leaves one partial.
@@ -775,6 +803,8 @@ hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
 hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
 // fb_consistency.hip
 hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
+// track_points.hip
+hipError_t launch_track_points(const TrackPointsArgs& a, hipStream_t s);
 // flow_metrics.hip
 hipError_t launch_flow_metrics(const FlowMetricsArgs& a, hipStream_t s);
 // augment.hip

@@ -10,6 +10,7 @@ from .consistency import fb_consistency, fb_consistency_ref  # noqa: F401
 from .corr import CorrPyramid, LocalCorrPyramid  # noqa: F401
 from .frame_io import flow_to_image, ingest_frames  # noqa: F401
 from .metrics import flow_metrics, flow_metrics_ref  # noqa: F401
+from .track import PointTracker, seed_points, track_points, track_points_ref  # noqa: F401
 from .upsample import convex_upsample, upflow8  # noqa: F401
 from .warm_start import forward_splat_nearest  # noqa: F401
 from . import reference  # noqa: F401

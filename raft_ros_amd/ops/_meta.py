@@ -224,6 +224,13 @@ def register() -> None:
         return (flow_fw.new_empty((B, H, W), dtype=torch.uint8), flow_fw.new_empty((B, H, W), dtype=torch.float32),
                 flow_fw.new_empty((B, 2), dtype=torch.int32))
 
+    @fake(lib + "track_points")
+    def _(pos, ids, age, epoch, flow_fw, flow_bw, left, top, w, h, S, alpha1, alpha2):
+        B, N = ids.shape
+        return (torch.empty_like(pos), torch.empty_like(pos), torch.empty_like(ids), torch.empty_like(age),
+                epoch.new_empty((1,)), pos.new_empty((B, N), dtype=torch.uint8), pos.new_empty((B, N)),
+                pos.new_empty((B, 4), dtype=torch.int32))
+
     @fake(lib + "flow_metrics")
     def _(flow_pr, flow_gt, valid, top, left):
         B = flow_gt.shape[0]

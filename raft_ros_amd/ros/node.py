@@ -22,6 +22,13 @@ Topics / parameters are those of the reference so existing launch files work:
   mask is published on ``/raft_occlusion`` (queue_size 100), encoding ``mono8``, with the header
   of the result: 0 = consistent, 128 = inconsistent (occluded or mismatched), 255 = the flow
   leaves the frame.  With the parameter off there is no second publisher.
+* ``/RAFT/track`` (default off) and ``/RAFT/track_cell`` (default 32): a grid of points, one per
+  cell of the image, is followed through the flow on the device (``ops/track.py``) and published
+  on ``/raft_tracks`` (queue_size 100) as ``sensor_msgs/PointCloud`` with the header of the result:
+  the tracked points ``(x, y, 0)`` in image coordinates with the channels ``id`` (``id mod 2^24``),
+  ``prev_x``, ``prev_y`` and ``age``.  Pairs are continuous by warm start's stamp rule; with
+  ``/RAFT/occlusion`` the forward-backward check drops inconsistent points.  With the parameter
+  off there is no third publisher.
 
 Pairing rule (reference :87-114): take the oldest current frame, then discard
 previous frames until one with a stamp strictly earlier than the current one is
@@ -48,6 +55,7 @@ import torch
 from ..models import RAFT
 from ..ops.consistency import OCC_LEVELS, fb_consistency
 from ..ops.frame_io import flow_to_image, ingest_frames
+from ..ops.track import PointTracker
 from ..ops.warm_start import forward_splat_nearest
 from ..runtime import GraphedRAFT
 from ..utils import checkpoint, flow_viz
@@ -114,7 +122,7 @@ class FlowInference:
 
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
                  mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False,
-                 device_io: bool = False, consistency: bool = False):
+                 device_io: bool = False, consistency: bool = False, track: bool = False, track_cell: int = 32):
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         self.device = torch.device(device)
@@ -142,6 +150,16 @@ class FlowInference:
         self.last_counts: Optional[np.ndarray] = None  # pixels of class 1 / 2 of the last visualize_checked
         self._pin_occ: Optional[torch.Tensor] = None
         self._pin_counts: Optional[torch.Tensor] = None
+        # point tracks (tracks / visualize_tracks): a grid of points, one per track_cell x track_cell
+        # cell of the unpadded image, kept on the device and advanced by every pair's flow
+        # (ops/track.py); continuous pairs are recognised by warm start's stamp rule
+        self.track = track
+        self.track_cell = int(track_cell)
+        self._tracker = PointTracker(S=self.track_cell) if track else None
+        self._track_stamp = None
+        self._track_shape = None
+        self._track_shift = None  # (roi, the fp32 (left, top) on the device)
+        self._pins = {}  # pinned return buffers of the tracks, by name
 
     def reset_warm_start(self) -> None:
         """Forget the previous pair: the next call runs cold."""
@@ -273,11 +291,92 @@ class FlowInference:
         rgb = flow_viz.flow_to_image(flo)
         return np.ascontiguousarray(rgb[:, :, [2, 1, 0]]).astype(np.uint8)
 
+    # ------------------------------------------------------------------ point tracks
+    def _tracks_device(self, prev: np.ndarray, curr: np.ndarray, prev_stamp, curr_stamp):
+        """One model run and one tracker step -> (flow_up of the run, the step's arrays in image
+        coordinates as device tensors).  The pair continues the last one when ``prev_stamp`` is
+        given and equals the last call's ``curr_stamp`` and the padded shape is unchanged (warm
+        start's rule); any other pair seeds the grid anew."""
+        if not self.track:
+            raise RuntimeError("tracks needs FlowInference(track=True)")
+        h, w = prev.shape[:2]
+        image1, image2 = self._padded_pair(prev, curr)
+        shape = tuple(image1.shape)
+        continuous = prev_stamp is not None and prev_stamp == self._track_stamp and shape == self._track_shape
+        flow_up = self._run(image1, image2, prev_stamp, curr_stamp, both=self.consistency)
+        pad = InputPadder((h, w))._pad
+        roi = (pad[0], pad[2], w, h)  # the unpadded image inside the padded frame
+        fw = flow_up[0:1].float().contiguous()
+        bw = flow_up[1:2].float().contiguous() if self.consistency else None
+        pos, prv, ids, age, _, status, _, _ = self._tracker.update(fw, bw, continuous=continuous, roi=roi)
+        self._track_stamp, self._track_shape = curr_stamp, shape
+        if self._track_shift is None or self._track_shift[0] != (roi, fw.device):
+            self._track_shift = ((roi, fw.device), torch.tensor([roi[0], roi[1]], dtype=torch.float32).to(fw.device))
+        shift = self._track_shift[1]
+        arrays = dict(points=(pos - shift)[0], prev=(prv - shift)[0], ids=ids[0], age=age[0], status=status[0])
+        return flow_up, arrays
+
+    def _to_pinned(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        pin = self._pins.get(name)
+        if pin is None or pin.shape != t.shape or pin.dtype != t.dtype:
+            pin = self._pins[name] = torch.empty(tuple(t.shape), dtype=t.dtype, pin_memory=True)
+        pin.copy_(t, non_blocking=True)
+        return pin
+
+    def tracks(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
+        """(flow of the padded pair, the point tracks of the unpadded image).
+
+        The tracks are numpy arrays over the N slots of the grid, in image coordinates (frame
+        coordinates minus the left / top pad): ``points`` (N, 2) fp32 (x, y) in the current frame,
+        ``prev`` (N, 2) where each was in the previous frame (NaN for a new point), ``ids`` (N,)
+        int64, ``age`` (N,) int32 and ``status`` (N,) uint8, the fate of the point the slot held
+        before: 0 tracked (the only slots whose ``prev`` is a correspondence), 1 inconsistent, 2 left
+        the image, 3 crowded out.  With ``consistency`` the model runs on the pair and the swapped
+        pair and the forward-backward check applies; otherwise only the frame test.  With
+        ``device_io`` the arrays come back through pinned buffers under one synchronisation."""
+        with torch.inference_mode():
+            flow_up, arrays = self._tracks_device(prev, curr, prev_stamp, curr_stamp)
+            if self._on_device:
+                pins = {k: self._to_pinned(k, v) for k, v in arrays.items()}
+                torch.cuda.current_stream(self.device).synchronize()
+                return flow_up[0:1], {k: p.numpy().copy() for k, p in pins.items()}  # the buffers are reused
+        return flow_up[0:1], {k: v.cpu().numpy().copy() for k, v in arrays.items()}
+
+    def visualize_tracks(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
+        """(the image ``visualize`` returns, the mask of ``visualize_checked`` or None without
+        ``consistency``, the tracks of ``tracks``) from one run of the model."""
+        with torch.inference_mode():
+            flow_up, arrays = self._tracks_device(prev, curr, prev_stamp, curr_stamp)
+            flow_fw = flow_up[0:1]
+            occ = counts = None
+            if self.consistency:
+                occ, _, counts = fb_consistency(flow_fw, flow_up[1:2])
+            if self._on_device:
+                pins = {k: self._to_pinned(k, v) for k, v in arrays.items()}
+                img = self._to_pinned("image", flow_to_image(flow_fw, convert_to_bgr=True)[0])
+                if occ is not None:
+                    occ, counts = self._to_pinned("occ", occ[0]), self._to_pinned("counts", counts[0])
+                torch.cuda.current_stream(self.device).synchronize()
+                if occ is not None:
+                    self.last_counts = counts.numpy().copy()
+                return (img.numpy().copy(), None if occ is None else OCC_LEVELS[occ.numpy()],
+                        {k: p.numpy().copy() for k, p in pins.items()})
+        rgb = flow_viz.flow_to_image(flow_fw[0].permute(1, 2, 0).float().cpu().numpy())
+        if occ is not None:
+            self.last_counts = counts[0].cpu().numpy().copy()
+        return (np.ascontiguousarray(rgb[:, :, [2, 1, 0]]).astype(np.uint8),
+                None if occ is None else OCC_LEVELS[occ[0].cpu().numpy()],
+                {k: v.cpu().numpy().copy() for k, v in arrays.items()})
+
 
 class RaftRosNode:
     """The ROS node; all ROS modules are injected at construction for testability."""
 
-    def __init__(self, rospy=None, image_msg=None, cv_bridge_cls=None, inference: Optional[FlowInference] = None):
+    def __init__(self, rospy=None, image_msg=None, cv_bridge_cls=None, inference: Optional[FlowInference] = None,
+                 track_msgs=None):
+        """``track_msgs``: the message classes (PointCloud, Point32, ChannelFloat32) of
+        ``/raft_tracks``; imported from sensor_msgs / geometry_msgs when ``/RAFT/track`` is set and
+        none are given."""
         if rospy is None:
             import rospy  # noqa: F811
         if image_msg is None:
@@ -294,6 +393,17 @@ class RaftRosNode:
         self.warm_start = bool(_get_param(rospy, "/RAFT/warm_start", False))
         self.occlusion = bool(_get_param(rospy, "/RAFT/occlusion", False))
         self._pub_occ = rospy.Publisher("/raft_occlusion", image_msg, queue_size=100) if self.occlusion else None
+        self.track = bool(_get_param(rospy, "/RAFT/track", False))
+        self.track_cell = int(_get_param(rospy, "/RAFT/track_cell", 32))
+        self._pub_tracks = None
+        if self.track:
+            if track_msgs is None:
+                from geometry_msgs.msg import Point32
+                from sensor_msgs.msg import ChannelFloat32, PointCloud
+
+                track_msgs = (PointCloud, Point32, ChannelFloat32)
+            self._track_msgs = track_msgs
+            self._pub_tracks = rospy.Publisher("/raft_tracks", track_msgs[0], queue_size=100)
         if inference is None:
             print("Initialize RAFT...")
             inference = FlowInference(rospy.get_param("/RAFT/weight_path"), bool(rospy.get_param("/RAFT/is_small")),
@@ -303,7 +413,8 @@ class RaftRosNode:
                                       hip_graph=bool(_get_param(rospy, "/RAFT/hip_graph", True)),
                                       warm_start=self.warm_start,
                                       device_io=bool(_get_param(rospy, "/RAFT/device_io", False)),
-                                      consistency=self.occlusion)
+                                      consistency=self.occlusion,
+                                      **(dict(track=True, track_cell=self.track_cell) if self.track else {}))
             print("Initialize RAFT finish!")
         self.inference = inference
         self._thread: Optional[threading.Thread] = None
@@ -319,9 +430,12 @@ class RaftRosNode:
         prev = self.bridge.imgmsg_to_cv2(prev_msg, desired_encoding="passthrough")
         curr = self.bridge.imgmsg_to_cv2(curr_msg, desired_encoding="passthrough")
         # the message stamps tell the inference whether pairs are continuous
-        stamps = dict(prev_stamp=_stamp_sec(prev_msg), curr_stamp=_stamp_sec(curr_msg)) if self.warm_start else {}
-        occ = None
-        if self.occlusion:
+        stamps = (dict(prev_stamp=_stamp_sec(prev_msg), curr_stamp=_stamp_sec(curr_msg))
+                  if self.warm_start or self.track else {})
+        occ = tracks = None
+        if self.track:
+            result, occ, tracks = self.inference.visualize_tracks(np.asarray(prev), np.asarray(curr), **stamps)
+        elif self.occlusion:
             result, occ = self.inference.visualize_checked(np.asarray(prev), np.asarray(curr), **stamps)
         else:
             result = self.inference.visualize(np.asarray(prev), np.asarray(curr), **stamps)
@@ -329,9 +443,26 @@ class RaftRosNode:
         header.frame_id = "raft_image"
         out = self.bridge.cv2_to_imgmsg(result, encoding="passthrough", header=header)
         self._pub.publish(out)
-        if occ is not None:
+        if occ is not None and self._pub_occ is not None:
             self._pub_occ.publish(self.bridge.cv2_to_imgmsg(occ, encoding="mono8", header=header))
+        if tracks is not None:
+            self._pub_tracks.publish(self.tracks_msg(tracks, header))
         return out
+
+    def tracks_msg(self, tracks, header):
+        """The tracked points (status 0) as a sensor_msgs/PointCloud: ``points[i] = (x, y, 0)`` in
+        the current frame, channels ``id`` (``id mod 2^24``: exact in float32), ``prev_x``,
+        ``prev_y`` (the same point in the previous frame) and ``age`` (pairs survived)."""
+        cloud_cls, point_cls, channel_cls = self._track_msgs
+        keep = tracks["status"] == 0
+        pts, prv = tracks["points"][keep], tracks["prev"][keep]
+        msg = cloud_cls()
+        msg.header = header
+        msg.points = [point_cls(x=float(x), y=float(y), z=0.0) for x, y in pts]
+        values = (("id", tracks["ids"][keep] % (1 << 24)), ("prev_x", prv[:, 0]), ("prev_y", prv[:, 1]),
+                  ("age", tracks["age"][keep]))
+        msg.channels = [channel_cls(name=name, values=np.asarray(v, dtype=np.float32).tolist()) for name, v in values]
+        return msg
 
     def thdInference(self, stop: Optional[Callable[[], bool]] = None) -> None:
         while not (stop and stop()) and not self.rospy.is_shutdown():
