@@ -16,7 +16,10 @@ forward-backward consistency mask is written beside the flow as ``occ_%04d.png``
 (0 consistent, 128 inconsistent, 255 the flow leaves the frame).  With ``--tracks`` a
 grid of points (one per ``--track_cell`` cell of the image) is followed through the
 flows on the device and the tracked points of every pair are written to
-``tracks.csv`` (``frame,id,x,y,prev_x,prev_y,age``, image coordinates).  ``--model`` is
+``tracks.csv`` (``frame,id,x,y,prev_x,prev_y,age``, image coordinates).  With ``--scale D``
+(an integer in 2..8) the model runs on the frames reduced by ``D`` and its flow is brought
+back to the frames' resolution and pixel units on the device (``ops/frame_scale.py``); the
+picture, the mask and the tracks are those of the unpadded frame.  ``--model`` is
 optional (random weights) so the pipeline can be smoke-tested without the
 pretrained files.
 """
@@ -36,6 +39,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from raft_ros_amd.models import RAFT  # noqa: E402
 from raft_ros_amd.ops.consistency import OCC_LEVELS, fb_consistency  # noqa: E402
 from raft_ros_amd.ops.frame_io import flow_to_image, ingest_frames  # noqa: E402
+from raft_ros_amd.ops.frame_scale import ingest_frames_scaled, upscale_flow  # noqa: E402
 from raft_ros_amd.ops.track import PointTracker  # noqa: E402
 from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
@@ -114,13 +118,21 @@ def demo(args):
     flow_prev = None  # --warm_start: the last pair's low-resolution flow, projected onto its second frame
     device_viz = getattr(args, "device_viz", False)
     occlusion = getattr(args, "occlusion", False)
+    scale = getattr(args, "scale", 1)
     # --tracks: consecutive pairs of the sorted directory are continuous; the tracker itself
     # starts over when the frame size changes
     tracker = PointTracker(S=getattr(args, "track_cell", 32)) if getattr(args, "tracks", False) else None
     rows = ["frame,id,x,y,prev_x,prev_y,age"]
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
-            if device_viz:
+            raw1 = None
+            if scale > 1:
+                # working resolution: the uint8 frames are reduced and padded by one launch; the
+                # model sees the low-resolution pair, everything after it the upscaled flow
+                raw1 = load_image(imfile1, args.device, raw=True)
+                pair, padder = ingest_frames_scaled([raw1, load_image(imfile2, args.device, raw=True)], scale)
+                image1, image2 = pair[0:1], pair[1:2]
+            elif device_viz:
                 pair, padder = ingest_frames([load_image(imfile1, args.device, raw=True),
                                               load_image(imfile2, args.device, raw=True)])
                 image1, image2 = pair[0:1], pair[1:2]
@@ -138,6 +150,8 @@ def demo(args):
                 init = None if flow_prev is None else torch.cat([flow_prev, torch.zeros_like(flow_prev)])
                 flow_low, flow_up = model(torch.cat([image1, image2]), torch.cat([image2, image1]), iters=args.iters,
                                           flow_init=init, test_mode=True)
+                if scale > 1:  # both directions in one call, onto the unpadded frame
+                    flow_up = upscale_flow(flow_up, padder, scale, raw1.shape[:2])
                 occ = fb_consistency(flow_up[0:1], flow_up[1:2])[0]
                 flow_bw = flow_up[1:2].float().contiguous()
                 flow_low, flow_up = flow_low[0:1], flow_up[0:1]
@@ -146,13 +160,19 @@ def demo(args):
                     Image.fromarray(mask, mode="L").save(os.path.join(args.output, "occ_%04d.png" % k))
             else:
                 flow_low, flow_up = model(image1, image2, iters=args.iters, flow_init=flow_prev, test_mode=True)
+                if scale > 1:
+                    flow_up = upscale_flow(flow_up, padder, scale, raw1.shape[:2])
             if warm:
                 flow_prev = forward_splat_nearest(flow_low)
             if tracker is not None:
                 # the points live in the unpadded image inside the padded frame; with --occlusion
                 # the forward-backward check drops inconsistent points
-                left, top = padder._pad[0], padder._pad[2]
-                roi = (left, top, padder.wd, padder.ht)
+                if scale > 1:  # the upscaled flow is the unpadded frame's: no pad shift
+                    left, top = 0, 0
+                    roi = (0, 0, raw1.shape[1], raw1.shape[0])
+                else:
+                    left, top = padder._pad[0], padder._pad[2]
+                    roi = (left, top, padder.wd, padder.ht)
                 pos, prv, ids, age, _, status, _, _ = tracker.update(flow_up.float().contiguous(), flow_bw, roi=roi)
                 pos, prv, ids, age, status = [t[0].cpu().numpy() for t in (pos, prv, ids, age, status)]
                 for j in np.flatnonzero(status == 0):
@@ -160,7 +180,9 @@ def demo(args):
                                                                  prv[j, 0] - left, prv[j, 1] - top, age[j]))
             out = os.path.join(args.output, "flow_%04d.png" % k)
             if rank == 0:
-                viz(image1, flow_up, out, show=args.show, device_viz=device_viz)
+                # --scale: the picture shows the raw frame above the upscaled flow
+                shown = image1 if raw1 is None else raw1.permute(2, 0, 1)[None].float()
+                viz(shown, flow_up, out, show=args.show, device_viz=device_viz)
             outs.append(out)
     if tracker is not None and rank == 0:
         with open(os.path.join(args.output, "tracks.csv"), "w") as f:
@@ -197,6 +219,9 @@ def main(argv=None):
                    help="follow a grid of points through the flows on the device and write the tracked points of "
                         "every pair to tracks.csv (frame,id,x,y,prev_x,prev_y,age; ops/track.py)")
     p.add_argument("--track_cell", type=int, default=32, help="with --tracks: the cell size, one point per cell")
+    p.add_argument("--scale", type=int, default=1, choices=range(1, 9), metavar="D",
+                   help="working resolution: run the model on the frames reduced by the integer factor D (1..8) and "
+                        "bring the flow back to the frames' resolution and pixel units (ops/frame_scale.py)")
     p.add_argument("--query_shard", action="store_true",
                    help="under torchrun: shard the correlation volume over the ranks' query pixels "
                         "(high-resolution inference; raft_ros_amd/parallel/query_shard.py)")

@@ -653,6 +653,31 @@ struct IngestArgs {
   int Hp, Wp;
 };
 
+// Working-resolution inference (csrc/frame_scale.hip).  Downscale: uint8 (N, H, W, 3) camera
+// frames -> fp32 (N, 3, h + pt + pb, w + pl + pr), h = ceil(H / D), w = ceil(W / D): cell (i, j)
+// is the mean of the in-image pixels of rows [iD, (i+1)D) x columns [jD, (j+1)D) (integer sum,
+// one fp32 division by the count), replicate padded.
+struct IngestScaledArgs {
+  const unsigned char* in;  // (N, H, W, 3) uint8
+  float* out;               // (N, 3, hp, wp) fp32
+  int N, H, W, D;
+  int h, w;    // ceil(H / D), ceil(W / D)
+  int pl, pt;  // left / top pad (right / bottom follow from hp, wp)
+  int hp, wp;
+};
+
+// Upscale: the model's flow on the padded low-resolution frame, fp32 (B, 2, hp, wp), read inside
+// the unpadded image [top, top + h) x [left, left + w) -> fp32 (B, 2, H, W) at the camera's
+// resolution and in its pixel units: bilinear with pixel centres aligned, clamped at the
+// border, times D.  The weights are num / (2 D) with integer num.
+struct UpscaleFlowArgs {
+  const float* flow;  // (B, 2, hp, wp) fp32
+  float* out;         // (B, 2, H, W) fp32
+  int B, D;
+  int hp, wp, left, top, w, h;
+  int H, W;  // ceil(H / D) == h, ceil(W / D) == w
+};
+
 // Forward-backward consistency of a flow pair (csrc/fb_consistency.hip): follow the forward
 // flow, read the backward flow there bilinearly; the two should cancel.
 struct FbConsistencyArgs {
@@ -801,6 +826,9 @@ hipError_t launch_forward_splat(const SplatArgs& a, hipStream_t s);
 // flow_color.hip
 hipError_t launch_flow_to_image(const FlowColorArgs& a, hipStream_t s);
 hipError_t launch_ingest_frames(const IngestArgs& a, hipStream_t s);
+// frame_scale.hip
+hipError_t launch_ingest_frames_scaled(const IngestScaledArgs& a, hipStream_t s);
+hipError_t launch_upscale_flow(const UpscaleFlowArgs& a, hipStream_t s);
 // fb_consistency.hip
 hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
 // track_points.hip

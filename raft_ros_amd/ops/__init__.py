@@ -9,6 +9,7 @@ from ._ext import is_loaded, library_path, load_error, use_native  # noqa: F401
 from .consistency import fb_consistency, fb_consistency_ref  # noqa: F401
 from .corr import CorrPyramid, LocalCorrPyramid  # noqa: F401
 from .frame_io import flow_to_image, ingest_frames  # noqa: F401
+from .frame_scale import ingest_frames_scaled, ingest_frames_scaled_ref, scaled_shape, upscale_flow, upscale_flow_ref  # noqa: F401
 from .metrics import flow_metrics, flow_metrics_ref  # noqa: F401
 from .track import PointTracker, seed_points, track_points, track_points_ref  # noqa: F401
 from .upsample import convex_upsample, upflow8  # noqa: F401

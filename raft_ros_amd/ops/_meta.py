@@ -218,6 +218,16 @@ def register() -> None:
         N, H, W, _ = frames.shape
         return frames.new_empty((N, 3, H + pad_t + pad_b, W + pad_l + pad_r), dtype=torch.float32)
 
+    @fake(lib + "ingest_frames_scaled")
+    def _(frames, scale, pad_l, pad_r, pad_t, pad_b):
+        N, H, W, _ = frames.shape
+        h, w = -(-H // scale), -(-W // scale)
+        return frames.new_empty((N, 3, h + pad_t + pad_b, w + pad_l + pad_r), dtype=torch.float32)
+
+    @fake(lib + "upscale_flow")
+    def _(flow, scale, left, top, w, h, H, W):
+        return flow.new_empty((flow.shape[0], 2, H, W))
+
     @fake(lib + "fb_consistency")
     def _(flow_fw, flow_bw, alpha1, alpha2):
         B, _, H, W = flow_fw.shape

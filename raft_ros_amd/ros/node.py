@@ -29,6 +29,11 @@ Topics / parameters are those of the reference so existing launch files work:
   ``prev_x``, ``prev_y`` and ``age``.  Pairs are continuous by warm start's stamp rule; with
   ``/RAFT/occlusion`` the forward-backward check drops inconsistent points.  With the parameter
   off there is no third publisher.
+* ``/RAFT/scale`` (default 1): the working resolution.  With an integer ``D`` in 2..8 the model runs
+  on the frames reduced by ``D`` (box filter, ``ops/frame_scale.py``) and its flow is brought back
+  to the camera's resolution and pixel units (bilinear, times ``D``) before anything else reads
+  it: the published image, the mask and the track coordinates are those of the unpadded camera
+  frame ``H x W``.  With 1 nothing changes.
 
 Pairing rule (reference :87-114): take the oldest current frame, then discard
 previous frames until one with a stamp strictly earlier than the current one is
@@ -55,6 +60,7 @@ import torch
 from ..models import RAFT
 from ..ops.consistency import OCC_LEVELS, fb_consistency
 from ..ops.frame_io import flow_to_image, ingest_frames
+from ..ops.frame_scale import ingest_frames_scaled, scaled_shape, upscale_flow
 from ..ops.track import PointTracker
 from ..ops.warm_start import forward_splat_nearest
 from ..runtime import GraphedRAFT
@@ -118,11 +124,21 @@ class FramePairer:
 
 
 class FlowInference:
-    """RAFT inference on numpy HxWx3 uint8 frames -> BGR uint8 flow visualisation."""
+    """RAFT inference on numpy HxWx3 uint8 frames -> BGR uint8 flow visualisation.
+
+    ``scale = D`` in 2..8 sets a working resolution: the model runs on the frames reduced by ``D``
+    (``ops/frame_scale.py``) and every public method passes its flow through ``upscale_flow`` once,
+    so that flows, images, masks and tracks are those of the *unpadded* camera frame ``H x W``
+    (not of the padded frame, as with ``scale = 1``), in the camera's pixel units.  Warm start
+    keeps working on the low-resolution flow."""
 
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
                  mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False,
-                 device_io: bool = False, consistency: bool = False, track: bool = False, track_cell: int = 32):
+                 device_io: bool = False, consistency: bool = False, track: bool = False, track_cell: int = 32,
+                 scale: int = 1):
+        if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 8:
+            raise ValueError(f"FlowInference: expected an integer scale in 1..8, got {scale!r}")
+        self.scale = scale
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         self.device = torch.device(device)
@@ -187,13 +203,19 @@ class FlowInference:
         with torch.cuda.device(self.device):
             frames = self._pin_in.to(self.device, non_blocking=True)
             self._pin_in_free.record()
-        images, _ = ingest_frames(frames)
+        images, _ = ingest_frames(frames) if self.scale == 1 else ingest_frames_scaled(frames, self.scale)
         return images[0:1], images[1:2]
 
     def _padded_pair(self, prev: np.ndarray, curr: np.ndarray):
-        """The two frames as the model takes them: (1, 3, Hp, Wp) fp32 on the device, padded."""
+        """The two frames as the model takes them: (1, 3, Hp, Wp) fp32 on the device, padded; with
+        ``scale > 1`` reduced to the working resolution first."""
         if self._on_device:
             return self._ingest(prev, curr)
+        if self.scale > 1:  # a plain uint8 upload, then the downscale where the model runs
+            frames = torch.stack([torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)),
+                                  torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8))]).to(self.device)
+            images, _ = ingest_frames_scaled(frames, self.scale)
+            return images[0:1], images[1:2]
         image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
         image2 = torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8)).permute(2, 0, 1).float()[None]
         image1, image2 = image1.to(self.device), image2.to(self.device)
@@ -228,12 +250,21 @@ class FlowInference:
             self._warm_stamp, self._warm_shape = curr_stamp, shape
         return flow_up
 
+    def _upscale(self, flow_up: torch.Tensor, frame: np.ndarray) -> torch.Tensor:
+        """``scale > 1``: the model's flow on the padded low-resolution frame -> the flow of the
+        unpadded camera frame (B, 2, H, W).  ``flow_up`` may be a captured graph's static output: the
+        op reads it now and writes a fresh tensor."""
+        H, W = frame.shape[:2]
+        return upscale_flow(flow_up, InputPadder(scaled_shape(H, W, self.scale)), self.scale, (H, W))
+
     @torch.inference_mode()
     def flow(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> torch.Tensor:
         """Flow of the padded pair.  With ``warm_start`` the call is warm only when ``prev_stamp``
         is given and equals the last call's ``curr_stamp`` and the padded shape is unchanged;
-        any other call runs cold and drops the kept state."""
-        return self._run(*self._padded_pair(prev, curr), prev_stamp, curr_stamp)
+        any other call runs cold and drops the kept state.  With ``scale > 1`` the result is the flow
+        of the unpadded camera frame, (1, 2, H, W)."""
+        flow_up = self._run(*self._padded_pair(prev, curr), prev_stamp, curr_stamp)
+        return flow_up if self.scale == 1 else self._upscale(flow_up, prev)
 
     @torch.inference_mode()
     def flow_checked(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
@@ -242,17 +273,20 @@ class FlowInference:
         The model runs once on the batch of the pair and the swapped pair; image 0 of its output is
         the forward flow (what ``flow()`` computes), image 1 the backward flow, and
         ``ops.consistency.fb_consistency`` checks one against the other.  With ``warm_start`` the
-        pairing rule is ``flow()``'s; only the forward direction is kept and only it starts warm."""
+        pairing rule is ``flow()``'s; only the forward direction is kept and only it starts warm.  With ``scale > 1`` both
+        directions are upscaled in one call and everything is of the unpadded camera frame."""
         if not self.consistency:
             raise RuntimeError("flow_checked needs FlowInference(consistency=True)")
         flow_up = self._run(*self._padded_pair(prev, curr), prev_stamp, curr_stamp, both=True)
+        if self.scale > 1:
+            flow_up = self._upscale(flow_up, prev)
         flow_fw = flow_up[0:1]
         occ, err2, counts = fb_consistency(flow_fw, flow_up[1:2])
         return flow_fw, occ, err2, counts
 
     def visualize_checked(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
         """(the image ``visualize`` returns, the mask as mono uint8 (H, W): 0 consistent, 128
-        inconsistent, 255 the flow leaves the frame).  The counts of the two classes are kept as
+        inconsistent, 255 the flow leaves the frame; ``H x W`` of the camera frame with ``scale > 1``).  The counts of the two classes are kept as
         ``last_counts``.  With ``device_io`` everything comes back through pinned buffers under
         one synchronisation."""
         if self._on_device:
@@ -278,7 +312,8 @@ class FlowInference:
 
     def visualize(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None) -> np.ndarray:
         """The published image: colour-coded flow of the *padded* pair, BGR uint8
-        (reference convert2Img + inferRAFT, ros/scripts/main.py:70-80,117-149)."""
+        (reference convert2Img + inferRAFT, ros/scripts/main.py:70-80,117-149).  With ``scale > 1``
+        the image is the unpadded camera frame's, ``H x W``, not the padded size."""
         if self._on_device:
             with torch.inference_mode():
                 img = flow_to_image(self.flow(prev, curr, prev_stamp, curr_stamp), convert_to_bgr=True)[0]
@@ -296,16 +331,23 @@ class FlowInference:
         """One model run and one tracker step -> (flow_up of the run, the step's arrays in image
         coordinates as device tensors).  The pair continues the last one when ``prev_stamp`` is
         given and equals the last call's ``curr_stamp`` and the padded shape is unchanged (warm
-        start's rule); any other pair seeds the grid anew."""
+        start's rule); any other pair seeds the grid anew.  With ``scale > 1`` the flow is the
+        upscaled one and the points live on the whole camera frame: no pad shift."""
         if not self.track:
             raise RuntimeError("tracks needs FlowInference(track=True)")
         h, w = prev.shape[:2]
         image1, image2 = self._padded_pair(prev, curr)
         shape = tuple(image1.shape)
+        if self.scale > 1:
+            shape += (h, w, self.scale)  # one low-resolution shape serves several camera sizes
         continuous = prev_stamp is not None and prev_stamp == self._track_stamp and shape == self._track_shape
         flow_up = self._run(image1, image2, prev_stamp, curr_stamp, both=self.consistency)
-        pad = InputPadder((h, w))._pad
-        roi = (pad[0], pad[2], w, h)  # the unpadded image inside the padded frame
+        if self.scale > 1:
+            flow_up = self._upscale(flow_up, prev)
+            roi = (0, 0, w, h)  # the camera frame itself
+        else:
+            pad = InputPadder((h, w))._pad
+            roi = (pad[0], pad[2], w, h)  # the unpadded image inside the padded frame
         fw = flow_up[0:1].float().contiguous()
         bw = flow_up[1:2].float().contiguous() if self.consistency else None
         pos, prv, ids, age, _, status, _, _ = self._tracker.update(fw, bw, continuous=continuous, roi=roi)
@@ -324,7 +366,8 @@ class FlowInference:
         return pin
 
     def tracks(self, prev: np.ndarray, curr: np.ndarray, prev_stamp=None, curr_stamp=None):
-        """(flow of the padded pair, the point tracks of the unpadded image).
+        """(flow of the padded pair -- with ``scale > 1`` of the unpadded camera frame --, the point
+        tracks of the unpadded image).
 
         The tracks are numpy arrays over the N slots of the grid, in image coordinates (frame
         coordinates minus the left / top pad): ``points`` (N, 2) fp32 (x, y) in the current frame,
@@ -395,6 +438,7 @@ class RaftRosNode:
         self._pub_occ = rospy.Publisher("/raft_occlusion", image_msg, queue_size=100) if self.occlusion else None
         self.track = bool(_get_param(rospy, "/RAFT/track", False))
         self.track_cell = int(_get_param(rospy, "/RAFT/track_cell", 32))
+        self.scale = int(_get_param(rospy, "/RAFT/scale", 1))
         self._pub_tracks = None
         if self.track:
             if track_msgs is None:
@@ -414,6 +458,7 @@ class RaftRosNode:
                                       warm_start=self.warm_start,
                                       device_io=bool(_get_param(rospy, "/RAFT/device_io", False)),
                                       consistency=self.occlusion,
+                                      **(dict(scale=self.scale) if self.scale != 1 else {}),
                                       **(dict(track=True, track_cell=self.track_cell) if self.track else {}))
             print("Initialize RAFT finish!")
         self.inference = inference
