@@ -16,7 +16,8 @@ forward-backward consistency mask is written beside the flow as ``occ_%04d.png``
 (0 consistent, 128 inconsistent, 255 the flow leaves the frame).  With ``--tracks`` a
 grid of points (one per ``--track_cell`` cell of the image) is followed through the
 flows on the device and the tracked points of every pair are written to
-``tracks.csv`` (``frame,id,x,y,prev_x,prev_y,age``, image coordinates).  With ``--scale D``
+``tracks.csv`` (``frame,id,x,y,prev_x,prev_y,age``, image coordinates); ``--track_seeds corners``
+starts every new point on the Shi-Tomasi corner of its cell and adds the column ``score``.  With ``--scale D``
 (an integer in 2..8) the model runs on the frames reduced by ``D`` and its flow is brought
 back to the frames' resolution and pixel units on the device (``ops/frame_scale.py``); the
 picture, the mask and the tracks are those of the unpadded frame.  ``--model`` is
@@ -40,6 +41,7 @@ from raft_ros_amd.models import RAFT  # noqa: E402
 from raft_ros_amd.ops.consistency import OCC_LEVELS, fb_consistency  # noqa: E402
 from raft_ros_amd.ops.frame_io import flow_to_image, ingest_frames  # noqa: E402
 from raft_ros_amd.ops.frame_scale import ingest_frames_scaled, upscale_flow  # noqa: E402
+from raft_ros_amd.ops.corners import corner_seeds, slot_scores  # noqa: E402
 from raft_ros_amd.ops.track import PointTracker  # noqa: E402
 from raft_ros_amd.ops.warm_start import forward_splat_nearest  # noqa: E402
 from raft_ros_amd.utils import checkpoint, flow_viz  # noqa: E402
@@ -122,7 +124,12 @@ def demo(args):
     # --tracks: consecutive pairs of the sorted directory are continuous; the tracker itself
     # starts over when the frame size changes
     tracker = PointTracker(S=getattr(args, "track_cell", 32)) if getattr(args, "tracks", False) else None
-    rows = ["frame,id,x,y,prev_x,prev_y,age"]
+    # --track_seeds corners: a new point starts on the Shi-Tomasi corner of its cell, found in the
+    # uint8 frames (ops/corners.py); tracks.csv gains the score each point was born with
+    corners = tracker is not None and getattr(args, "track_seeds", "grid") == "corners"
+    min_score = getattr(args, "track_min_score", 0)
+    born = None
+    rows = ["frame,id,x,y,prev_x,prev_y,age" + (",score" if corners else "")]
     with torch.inference_mode():
         for k, (imfile1, imfile2) in enumerate(zip(images[:-1], images[1:])):
             raw1 = None
@@ -173,11 +180,26 @@ def demo(args):
                 else:
                     left, top = padder._pad[0], padder._pad[2]
                     roi = (left, top, padder.wd, padder.ht)
-                pos, prv, ids, age, _, status, _, _ = tracker.update(flow_up.float().contiguous(), flow_bw, roi=roi)
+                seeds = {}
+                if corners:
+                    # the first frame's corners serve a fresh grid, the second frame's the points born
+                    # in this step
+                    pair8 = torch.stack([load_image(imfile1, args.device, raw=True),
+                                         load_image(imfile2, args.device, raw=True)])
+                    found, cell_score = corner_seeds(pair8, tracker.S, roi[2:], (left, top), min_score=min_score)
+                    seeds = dict(first_seeds=found[0:1], seeds=found[1:2])
+                    resets = tracker.resets
+                pos, prv, ids, age, _, status, _, _ = tracker.update(flow_up.float().contiguous(), flow_bw, roi=roi,
+                                                                    **seeds)
+                if corners:
+                    born = slot_scores(pos, age, born if tracker.resets == resets else cell_score[0:1],
+                                       cell_score[1:2], roi, tracker.S)
+                    score = born[0].cpu().numpy()
                 pos, prv, ids, age, status = [t[0].cpu().numpy() for t in (pos, prv, ids, age, status)]
                 for j in np.flatnonzero(status == 0):
                     rows.append("%d,%d,%.3f,%.3f,%.3f,%.3f,%d" % (k, ids[j], pos[j, 0] - left, pos[j, 1] - top,
-                                                                 prv[j, 0] - left, prv[j, 1] - top, age[j]))
+                                                                 prv[j, 0] - left, prv[j, 1] - top, age[j])
+                                + (",%d" % score[j] if corners else ""))
             out = os.path.join(args.output, "flow_%04d.png" % k)
             if rank == 0:
                 # --scale: the picture shows the raw frame above the upscaled flow
@@ -219,6 +241,12 @@ def main(argv=None):
                    help="follow a grid of points through the flows on the device and write the tracked points of "
                         "every pair to tracks.csv (frame,id,x,y,prev_x,prev_y,age; ops/track.py)")
     p.add_argument("--track_cell", type=int, default=32, help="with --tracks: the cell size, one point per cell")
+    p.add_argument("--track_seeds", default="grid", choices=["grid", "corners"],
+                   help="with --tracks: where a new point starts: the centre of its cell (grid) or the cell's "
+                        "Shi-Tomasi corner, found on the device (ops/corners.py); with corners tracks.csv gains "
+                        "the column score, the corner score the point was born with")
+    p.add_argument("--track_min_score", type=int, default=0,
+                   help="with --track_seeds corners: a cell whose best score is not above this keeps its centre")
     p.add_argument("--scale", type=int, default=1, choices=range(1, 9), metavar="D",
                    help="working resolution: run the model on the frames reduced by the integer factor D (1..8) and "
                         "bring the flow back to the frames' resolution and pixel units (ops/frame_scale.py)")

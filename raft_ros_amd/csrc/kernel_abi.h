@@ -701,6 +701,8 @@ struct TrackPointsArgs {
   const long long* epoch; // (1)
   const float* fw;        // (B, 2, H, W) fp32 forward flow
   const float* bw;        // (B, 2, H, W) fp32 backward flow, or null: only the frame test applies
+  const float* seeds;     // (B, N, 2) fp32: where a fresh point of each cell starts, or null: the
+                          //   clamped centre of the cell
   float* pos_out;         // (B, N, 2); phase 1 leaves the target q of every slot here
   float* prev;            // (B, N, 2): the position on entry, (NaN, NaN) for a re-seeded slot
   long long* ids_out;     // (B, N)
@@ -717,6 +719,21 @@ struct TrackPointsArgs {
   int left, top, w, h;    // roi inside the frame
   int S, Gx, Gy;          // cell size and grid: Gx = ceil(w / S), Gy = ceil(h / S), N = Gy * Gx
   long HW;                // H * W
+};
+
+// Corner seeds (csrc/corner_seeds.hip): per cell of the tracker's grid over the roi
+// [0, w) x [0, h) of the frame, the candidate pixel with the largest integer Shi-Tomasi score.
+struct CornerSeedsArgs {
+  const unsigned char* frames;  // (B, H, W, 3) uint8, no alignment assumed
+  unsigned long long* keys;     // (B, N) workspace, zeroed per call: score << 32 | (0xffffffff - (y * w + x))
+                                //   of the cell's winner; 0 = no candidate
+  float* seeds;                 // (B, N, 2) fp32 (x, y), the origin added
+  int* score;                   // (B, N) the winner's score, -1 without candidates
+  long long min_score;          // the winner is taken when score > min_score, else the cell's clamped centre
+  int B, N, H, W;
+  int w, h;                     // roi size, 1 <= w <= W, 1 <= h <= H
+  int left, top;                // origin added to the seeds
+  int S, Gx, Gy, margin;        // cells as in TrackPointsArgs; candidates have offsets in [margin, S - 1 - margin]
 };
 
 // Validation metrics of a padded prediction against ground truth (csrc/flow_metrics.hip): the
@@ -833,6 +850,8 @@ hipError_t launch_upscale_flow(const UpscaleFlowArgs& a, hipStream_t s);
 hipError_t launch_fb_consistency(const FbConsistencyArgs& a, hipStream_t s);
 // track_points.hip
 hipError_t launch_track_points(const TrackPointsArgs& a, hipStream_t s);
+// corner_seeds.hip
+hipError_t launch_corner_seeds(const CornerSeedsArgs& a, hipStream_t s);
 // flow_metrics.hip
 hipError_t launch_flow_metrics(const FlowMetricsArgs& a, hipStream_t s);
 // augment.hip

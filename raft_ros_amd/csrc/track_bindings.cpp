@@ -19,11 +19,12 @@ using TrackOut =
 // pos (B, N, 2) fp32, ids (B, N) int64, age (B, N) int32, epoch (1) int64, flow_fw and optionally
 // flow_bw (B, 2, H, W) fp32, the roi (left, top, w, h) and the cell size S -> pos_out, prev,
 // ids_out, age_out, epoch_out, status (B, N) uint8, err2 (B, N) fp32, counts (B, 4) int32.
-// Three launches on the current stream, no host read-back.
-TrackOut track_points(const at::Tensor& pos, const at::Tensor& ids, const at::Tensor& age, const at::Tensor& epoch,
-                      const at::Tensor& flow_fw, const std::optional<at::Tensor>& flow_bw, int64_t left, int64_t top,
-                      int64_t w, int64_t h, int64_t S, double alpha1, double alpha2) {
-  const char* op = "raft_amd::track_points: ";
+// Three launches on the current stream, no host read-back.  ``seeds`` (B, N, 2) fp32, where the
+// fresh point of every cell starts, or null: the cell's clamped centre.  The one body of both ops.
+static TrackOut track_points_impl(const char* op, const at::Tensor& pos, const at::Tensor& ids, const at::Tensor& age,
+                                  const at::Tensor& epoch, const at::Tensor& flow_fw,
+                                  const std::optional<at::Tensor>& flow_bw, const at::Tensor* seeds, int64_t left,
+                                  int64_t top, int64_t w, int64_t h, int64_t S, double alpha1, double alpha2) {
   TORCH_CHECK(flow_fw.is_cuda() && flow_fw.scalar_type() == at::kFloat && flow_fw.dim() == 4 &&
                   flow_fw.size(1) == 2 && flow_fw.is_contiguous(),
               op, "flow_fw must be a contiguous fp32 (B, 2, H, W) CUDA tensor");
@@ -57,6 +58,12 @@ TrackOut track_points(const at::Tensor& pos, const at::Tensor& ids, const at::Te
                   age.device() == flow_fw.device() && epoch.device() == flow_fw.device(),
               op, "all tensors must be on one device");
   TORCH_CHECK(B * N < (1L << 31), op, "B * N too large");
+  if (seeds != nullptr) {
+    TORCH_CHECK(seeds->is_cuda() && seeds->scalar_type() == at::kFloat && seeds->is_contiguous() &&
+                    seeds->dim() == 3 && seeds->size(0) == B && seeds->size(1) == N && seeds->size(2) == 2,
+                op, "seeds must be a contiguous fp32 (", B, ", ", N, ", 2) CUDA tensor, got ", seeds->sizes());
+    TORCH_CHECK(seeds->device() == flow_fw.device(), op, "all tensors must be on one device");
+  }
   c10::DeviceGuard guard(flow_fw.device());
   at::Tensor pos_out = at::empty({B, N, 2}, pos.options());
   at::Tensor prev = at::empty({B, N, 2}, pos.options());
@@ -79,6 +86,7 @@ TrackOut track_points(const at::Tensor& pos, const at::Tensor& ids, const at::Te
   a.epoch = reinterpret_cast<const long long*>(epoch.data_ptr<int64_t>());
   a.fw = flow_fw.data_ptr<float>();
   a.bw = has_bw ? flow_bw->data_ptr<float>() : nullptr;
+  a.seeds = seeds != nullptr ? seeds->data_ptr<float>() : nullptr;
   a.pos_out = pos_out.data_ptr<float>();
   a.prev = prev.data_ptr<float>();
   a.ids_out = reinterpret_cast<long long*>(ids_out.data_ptr<int64_t>());
@@ -108,6 +116,21 @@ TrackOut track_points(const at::Tensor& pos, const at::Tensor& ids, const at::Te
   return {pos_out, prev, ids_out, age_out, epoch_out, status, err2, counts};
 }
 
+TrackOut track_points(const at::Tensor& pos, const at::Tensor& ids, const at::Tensor& age, const at::Tensor& epoch,
+                      const at::Tensor& flow_fw, const std::optional<at::Tensor>& flow_bw, int64_t left, int64_t top,
+                      int64_t w, int64_t h, int64_t S, double alpha1, double alpha2) {
+  return track_points_impl("raft_amd::track_points: ", pos, ids, age, epoch, flow_fw, flow_bw, nullptr, left, top, w,
+                           h, S, alpha1, alpha2);
+}
+
+TrackOut track_points_seeded(const at::Tensor& pos, const at::Tensor& ids, const at::Tensor& age,
+                             const at::Tensor& epoch, const at::Tensor& flow_fw,
+                             const std::optional<at::Tensor>& flow_bw, const at::Tensor& seeds, int64_t left,
+                             int64_t top, int64_t w, int64_t h, int64_t S, double alpha1, double alpha2) {
+  return track_points_impl("raft_amd::track_points_seeded: ", pos, ids, age, epoch, flow_fw, flow_bw, &seeds, left,
+                           top, w, h, S, alpha1, alpha2);
+}
+
 }  // namespace raft_amd
 
 TORCH_LIBRARY_FRAGMENT(raft_amd, m) {
@@ -115,8 +138,13 @@ TORCH_LIBRARY_FRAGMENT(raft_amd, m) {
       "track_points(Tensor pos, Tensor ids, Tensor age, Tensor epoch, Tensor flow_fw, Tensor? flow_bw, int left, "
       "int top, int w, int h, int S, float alpha1, float alpha2) -> (Tensor pos_out, Tensor prev, Tensor ids_out, "
       "Tensor age_out, Tensor epoch_out, Tensor status, Tensor err2, Tensor counts)");
+  m.def(
+      "track_points_seeded(Tensor pos, Tensor ids, Tensor age, Tensor epoch, Tensor flow_fw, Tensor? flow_bw, "
+      "Tensor seeds, int left, int top, int w, int h, int S, float alpha1, float alpha2) -> (Tensor pos_out, "
+      "Tensor prev, Tensor ids_out, Tensor age_out, Tensor epoch_out, Tensor status, Tensor err2, Tensor counts)");
 }
 
 TORCH_LIBRARY_IMPL(raft_amd, CUDA, m) {
   m.impl("track_points", &raft_amd::track_points);
+  m.impl("track_points_seeded", &raft_amd::track_points_seeded);
 }

@@ -18,7 +18,8 @@
 //   a survivor that owns its cell: status 0, pos_out = q, prev = p, id kept, age + 1; any other
 //   survivor: status 3.  The slots whose status is not 0 are as many as the unowned cells: the
 //   k-th such slot in slot order takes the k-th unowned cell in cell order (two exclusive scans),
-//   pos_out = the seed of that cell, prev = NaN, id = epoch * N + slot, age = 0.
+//   pos_out = the seed of that cell (seeds[b, cell] when the caller gives seeds, else the cell's
+//   clamped centre), prev = NaN, id = epoch * N + slot, age = 0.
 //   counts[b] = the slots per status, from integer sums in LDS.
 // epoch_out = epoch + 1 is written by one thread of phase 1, which reads epoch nowhere else.
 //
@@ -181,11 +182,16 @@ __global__ __launch_bounds__(kTrackBlock2) void track_phase2_kernel(TrackPointsA
       a.age_out[i] = a.age[i] + 1;
     } else if (lost && k < nfree) {  // always: the lost slots are as many as the unowned cells
       const int cell = free_cells[k];
-      const int gy = cell / a.Gx, gx = cell - gy * a.Gx;
-      // the seed of the cell: its centre, clamped into a partial cell (64-bit: S may be huge)
-      const long cx = (long)gx * a.S + a.S / 2, cy = (long)gy * a.S + a.S / 2;
-      a.pos_out[2 * i] = (float)(a.left + (int)(cx < a.w - 1 ? cx : a.w - 1));
-      a.pos_out[2 * i + 1] = (float)(a.top + (int)(cy < a.h - 1 ? cy : a.h - 1));
+      if (a.seeds != nullptr) {  // the caller's seed of the cell
+        a.pos_out[2 * i] = a.seeds[2 * (off + cell)];
+        a.pos_out[2 * i + 1] = a.seeds[2 * (off + cell) + 1];
+      } else {
+        const int gy = cell / a.Gx, gx = cell - gy * a.Gx;
+        // the seed of the cell: its centre, clamped into a partial cell (64-bit: S may be huge)
+        const long cx = (long)gx * a.S + a.S / 2, cy = (long)gy * a.S + a.S / 2;
+        a.pos_out[2 * i] = (float)(a.left + (int)(cx < a.w - 1 ? cx : a.w - 1));
+        a.pos_out[2 * i + 1] = (float)(a.top + (int)(cy < a.h - 1 ? cy : a.h - 1));
+      }
       a.prev[2 * i] = __builtin_nanf("");
       a.prev[2 * i + 1] = __builtin_nanf("");
       a.ids_out[i] = epoch * (long long)N + slot;

@@ -7,6 +7,7 @@ numerical oracle in tests.
 """
 from ._ext import is_loaded, library_path, load_error, use_native  # noqa: F401
 from .consistency import fb_consistency, fb_consistency_ref  # noqa: F401
+from .corners import corner_seeds, corner_seeds_ref  # noqa: F401
 from .corr import CorrPyramid, LocalCorrPyramid  # noqa: F401
 from .frame_io import flow_to_image, ingest_frames  # noqa: F401
 from .frame_scale import ingest_frames_scaled, ingest_frames_scaled_ref, scaled_shape, upscale_flow, upscale_flow_ref  # noqa: F401

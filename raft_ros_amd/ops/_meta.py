@@ -241,6 +241,19 @@ def register() -> None:
                 epoch.new_empty((1,)), pos.new_empty((B, N), dtype=torch.uint8), pos.new_empty((B, N)),
                 pos.new_empty((B, 4), dtype=torch.int32))
 
+    @fake(lib + "track_points_seeded")
+    def _(pos, ids, age, epoch, flow_fw, flow_bw, seeds, left, top, w, h, S, alpha1, alpha2):
+        B, N = ids.shape
+        return (torch.empty_like(pos), torch.empty_like(pos), torch.empty_like(ids), torch.empty_like(age),
+                epoch.new_empty((1,)), pos.new_empty((B, N), dtype=torch.uint8), pos.new_empty((B, N)),
+                pos.new_empty((B, 4), dtype=torch.int32))
+
+    @fake(lib + "corner_seeds")
+    def _(frames, S, w, h, left, top, margin, min_score):
+        B = frames.shape[0]
+        N = (-(-h // S)) * (-(-w // S))
+        return frames.new_empty((B, N, 2), dtype=torch.float32), frames.new_empty((B, N), dtype=torch.int32)
+
     @fake(lib + "flow_metrics")
     def _(flow_pr, flow_gt, valid, top, left):
         B = flow_gt.shape[0]

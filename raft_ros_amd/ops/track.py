@@ -27,7 +27,8 @@ Per slot, all in fp32 (``fw`` and ``bw`` are read bilinearly with ``fb_consisten
     (0xffffffff - age) << 32 | slot; the smallest key owns the cell (the oldest, then the lowest slot)
     owner: status 0, pos_out = q, prev = p, id kept, age + 1;  other survivors: status 3
     the k-th slot (in slot order) whose status is not 0 takes the k-th unowned cell (in cell order):
-    pos_out = its seed, prev = (NaN, NaN), id = epoch * N + slot, age = 0
+    pos_out = its seed (the cell's clamped centre, or seeds[b, cell]), prev = (NaN, NaN),
+    id = epoch * N + slot, age = 0
     epoch_out = epoch + 1
 """
 from __future__ import annotations
@@ -68,14 +69,34 @@ def _seed_xy(roi: Roi, S: int, device) -> torch.Tensor:
     return torch.stack([sx[None, :].expand(Gy, Gx), sy[:, None].expand(Gy, Gx)], dim=-1).reshape(Gy * Gx, 2).float()
 
 
-def seed_points(B: int, roi: Sequence[int], S: int, device=None):
+def _check_seeds(seeds, B: int, N: int, device) -> None:
+    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.float32:
+        raise ValueError(f"track_points: expected seeds as a torch.float32 tensor, got "
+                         f"{seeds.dtype if isinstance(seeds, torch.Tensor) else type(seeds).__name__}")
+    if tuple(seeds.shape) != (B, N, 2):
+        raise ValueError(f"track_points: expected seeds of shape {(B, N, 2)}, got {tuple(seeds.shape)}")
+    if device is not None and seeds.device != torch.device(device):
+        raise ValueError(f"track_points: seeds are on {seeds.device}, the state on {device}")
+    if not seeds.is_contiguous():
+        raise ValueError("track_points: seeds must be contiguous")
+
+
+def seed_points(B: int, roi: Sequence[int], S: int, device=None, seeds: Optional[torch.Tensor] = None):
     """The initial state (pos (B, N, 2) fp32, ids (B, N) int64, age (B, N) int32, epoch (1,) int64):
-    slot ``j`` at the seed of cell ``j``, ``ids = j``, ``age = 0``, ``epoch = 1``."""
+    slot ``j`` at the seed of cell ``j`` (``seeds[:, j]`` when ``seeds`` (B, N, 2) fp32 is given, else
+    the cell's clamped centre), ``ids = j``, ``age = 0``, ``epoch = 1``."""
     roi = _check_grid(roi, S)
     S = int(S)
-    seeds = _seed_xy(roi, S, device)
-    N = seeds.shape[0]
-    pos = seeds[None].expand(B, N, 2).contiguous()
+    if seeds is None:
+        centres = _seed_xy(roi, S, device)
+        N = centres.shape[0]
+        pos = centres[None].expand(B, N, 2).contiguous()
+    else:
+        Gy, Gx = grid_shape(roi, S)
+        N = Gy * Gx
+        device = seeds.device if device is None and isinstance(seeds, torch.Tensor) else device
+        _check_seeds(seeds, B, N, device)
+        pos = seeds.clone()
     ids = torch.arange(N, dtype=torch.int64, device=device)[None].expand(B, N).contiguous()
     age = torch.zeros((B, N), dtype=torch.int32, device=device)
     epoch = torch.ones((1,), dtype=torch.int64, device=device)
@@ -111,7 +132,7 @@ def _bilinear(planes: torch.Tensor, x: torch.Tensor, y: torch.Tensor, H: int, W:
 def track_points_ref(pos: torch.Tensor, ids: torch.Tensor, age: torch.Tensor, epoch: torch.Tensor,
                      flow_fw: torch.Tensor, flow_bw: Optional[torch.Tensor] = None,
                      roi: Optional[Sequence[int]] = None, S: int = 32, alpha1: float = ALPHA1,
-                     alpha2: float = ALPHA2):
+                     alpha2: float = ALPHA2, seeds: Optional[torch.Tensor] = None):
     """One step as torch ops -> (pos_out, prev, ids_out, age_out, epoch_out, status, err2, counts).
 
     Every line is one rounding step of the kernel: no ``lerp``, ``addcmul`` or ``grid_sample``,
@@ -176,7 +197,10 @@ def track_points_ref(pos: torch.Tensor, ids: torch.Tensor, age: torch.Tensor, ep
     free_cells = torch.zeros((B, N + 1), dtype=torch.int64, device=dev)  # column N takes the owned cells
     free_cells = free_cells.scatter(1, torch.where(unowned, urank, torch.full_like(urank, N)), slots)
     new_cell = free_cells.gather(1, torch.where(lost, rank, torch.zeros_like(rank)))
-    seeds = _seed_xy(roi, S, dev)[new_cell]  # (B, N, 2)
+    if seeds is None:
+        seeds = _seed_xy(roi, S, dev)[new_cell]  # (B, N, 2)
+    else:  # the caller's seed of every cell
+        seeds = seeds.gather(1, new_cell[..., None].expand(B, N, 2))
     nan = torch.full((), float("nan"), **f32)
     own2 = owner[..., None]
     pos_out = torch.where(own2, torch.stack([qx, qy], dim=-1), seeds)
@@ -226,7 +250,8 @@ def _check_args(pos, ids, age, epoch, flow_fw, flow_bw, roi, S) -> Roi:
 
 def track_points(pos: torch.Tensor, ids: torch.Tensor, age: torch.Tensor, epoch: torch.Tensor,
                  flow_fw: torch.Tensor, flow_bw: Optional[torch.Tensor] = None,
-                 roi: Optional[Sequence[int]] = None, S: int = 32, alpha1: float = ALPHA1, alpha2: float = ALPHA2):
+                 roi: Optional[Sequence[int]] = None, S: int = 32, alpha1: float = ALPHA1, alpha2: float = ALPHA2,
+                 seeds: Optional[torch.Tensor] = None):
     """One step of the point grid -> (pos_out, prev, ids_out, age_out, epoch_out, status, err2, counts).
 
     ``pos`` (B, N, 2) fp32 (x, y) in frame coordinates, ``ids`` (B, N) int64 >= 0, ``age`` (B, N)
@@ -236,12 +261,18 @@ def track_points(pos: torch.Tensor, ids: torch.Tensor, age: torch.Tensor, epoch:
     slot held on entry: 0 tracked, 1 inconsistent, 2 left the roi, 3 crowded out; ``err2`` (B, N)
     its squared forward-backward error (+inf for status 2, 0 without ``flow_bw``); ``counts``
     (B, 4) int32 the slots per status.  Slots of status 0 keep their id; all others hold a new
-    point (``age = 0``, ``prev = NaN``)."""
+    point (``age = 0``, ``prev = NaN``), which starts at the clamped centre of its cell or, with
+    ``seeds`` (B, N, 2) fp32 (``ops/corners.py``), at ``seeds[b, cell]``."""
     roi = _check_args(pos, ids, age, epoch, flow_fw, flow_bw, roi, S)
+    if seeds is not None:
+        _check_seeds(seeds, ids.shape[0], ids.shape[1], flow_fw.device)
     if use_native(flow_fw):
+        if seeds is not None:
+            return tuple(ops().track_points_seeded(pos, ids, age, epoch, flow_fw, flow_bw, seeds, roi[0], roi[1],
+                                                   roi[2], roi[3], int(S), float(alpha1), float(alpha2)))
         return tuple(ops().track_points(pos, ids, age, epoch, flow_fw, flow_bw, roi[0], roi[1], roi[2], roi[3],
                                         int(S), float(alpha1), float(alpha2)))
-    return track_points_ref(pos, ids, age, epoch, flow_fw, flow_bw, roi, int(S), float(alpha1), float(alpha2))
+    return track_points_ref(pos, ids, age, epoch, flow_fw, flow_bw, roi, int(S), float(alpha1), float(alpha2), seeds)
 
 
 class PointTracker:
@@ -253,7 +284,12 @@ class PointTracker:
     changed: the points start at their seeds in the pair's first frame, with fresh ids, and take
     that pair's step.  Ids are never reused: ``epoch`` survives a reset (with another grid size it
     moves on to the first epoch whose ids lie above every id handed out so far; the bound is kept
-    on the host, nothing is read back)."""
+    on the host, nothing is read back).
+
+    ``seeds`` and ``first_seeds`` (B, N, 2) fp32, e.g. of ``ops.corners.corner_seeds``, replace the
+    cells' centres: ``seeds`` serves the points born in this step, which live in the pair's second
+    frame; ``first_seeds`` serves a (re)seeding of the grid, whose points start in the pair's first
+    frame, and is not read by a pair that continues the last one."""
 
     def __init__(self, S: int = 32, roi: Optional[Sequence[int]] = None, alpha1: float = ALPHA1,
                  alpha2: float = ALPHA2):
@@ -271,8 +307,8 @@ class PointTracker:
         """Forget the points: the next update seeds the grid (with new ids)."""
         self._state = None
 
-    def _seed(self, B: int, roi: Roi, device):
-        pos, ids, age, epoch = seed_points(B, roi, self.S, device)
+    def _seed(self, B: int, roi: Roi, device, seeds=None):
+        pos, ids, age, epoch = seed_points(B, roi, self.S, device, seeds)
         N = ids.shape[1]
         # the ids handed out so far are below _next_id: start at the first epoch whose ids lie above
         e0 = -(-self._next_id // N)
@@ -284,7 +320,8 @@ class PointTracker:
         return pos, ids, age, epoch
 
     def update(self, flow_fw: torch.Tensor, flow_bw: Optional[torch.Tensor] = None, continuous: bool = True,
-               roi: Optional[Sequence[int]] = None):
+               roi: Optional[Sequence[int]] = None, seeds: Optional[torch.Tensor] = None,
+               first_seeds: Optional[torch.Tensor] = None):
         if roi is not None:
             self.roi = tuple(int(v) for v in roi)
         B, _, H, W = flow_fw.shape
@@ -292,10 +329,10 @@ class PointTracker:
         sig = (B, H, W, flow_fw.device, use_roi, self.S)
         seeded = self._state is None or not continuous or sig != self._sig
         if seeded:
-            self._state = self._seed(B, use_roi, flow_fw.device)
+            self._state = self._seed(B, use_roi, flow_fw.device, first_seeds)
             self._sig = sig
         pos, ids, age, epoch = self._state
-        out = track_points(pos, ids, age, epoch, flow_fw, flow_bw, use_roi, self.S, self.alpha1, self.alpha2)
+        out = track_points(pos, ids, age, epoch, flow_fw, flow_bw, use_roi, self.S, self.alpha1, self.alpha2, seeds)
         pos_out, prev, ids_out, age_out, epoch_out, status, err2, counts = out
         self._state = (pos_out, ids_out, age_out, epoch_out)
         self._next_id += ids.shape[1]  # a step hands out ids below (epoch + 1) * N

@@ -29,6 +29,11 @@ Topics / parameters are those of the reference so existing launch files work:
   ``prev_x``, ``prev_y`` and ``age``.  Pairs are continuous by warm start's stamp rule; with
   ``/RAFT/occlusion`` the forward-backward check drops inconsistent points.  With the parameter
   off there is no third publisher.
+* ``/RAFT/track_seeds`` (default ``grid``): where a new point starts.  ``grid`` is the centre of
+  its cell; ``corners`` is the cell's Shi-Tomasi corner, found on the device from the uint8 frames
+  (``ops/corners.py``), and ``/raft_tracks`` gets a further channel ``score``, the corner score each
+  point was born with.  ``/RAFT/track_min_score`` (default 0): cells whose best score is not above
+  it keep their centre.
 * ``/RAFT/scale`` (default 1): the working resolution.  With an integer ``D`` in 2..8 the model runs
   on the frames reduced by ``D`` (box filter, ``ops/frame_scale.py``) and its flow is brought back
   to the camera's resolution and pixel units (bilinear, times ``D``) before anything else reads
@@ -59,6 +64,7 @@ import torch
 
 from ..models import RAFT
 from ..ops.consistency import OCC_LEVELS, fb_consistency
+from ..ops.corners import corner_seeds, slot_scores
 from ..ops.frame_io import flow_to_image, ingest_frames
 from ..ops.frame_scale import ingest_frames_scaled, scaled_shape, upscale_flow
 from ..ops.track import PointTracker
@@ -135,7 +141,9 @@ class FlowInference:
     def __init__(self, weight_path: Optional[str], small: bool = False, device: str = "cuda", iters: int = 20,
                  mixed_precision: bool = False, hip_graph: bool = True, warm_start: bool = False,
                  device_io: bool = False, consistency: bool = False, track: bool = False, track_cell: int = 32,
-                 scale: int = 1):
+                 scale: int = 1, track_seeds: str = "grid", track_min_score: int = 0):
+        if track_seeds not in ("grid", "corners"):
+            raise ValueError(f"FlowInference: track_seeds is 'grid' or 'corners', got {track_seeds!r}")
         if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 8:
             raise ValueError(f"FlowInference: expected an integer scale in 1..8, got {scale!r}")
         self.scale = scale
@@ -176,6 +184,13 @@ class FlowInference:
         self._track_shape = None
         self._track_shift = None  # (roi, the fp32 (left, top) on the device)
         self._pins = {}  # pinned return buffers of the tracks, by name
+        # where a new point starts: "grid", the centre of its cell, or "corners", the cell's
+        # Shi-Tomasi corner in the uint8 camera frame (ops/corners.py); with corners a sixth array,
+        # the score each point was born with, is kept next to the tracker's state
+        self.track_seeds = track_seeds
+        self.track_min_score = int(track_min_score)
+        self._frames_u8: Optional[torch.Tensor] = None  # the uint8 pair of the last upload, on the device
+        self._track_score: Optional[torch.Tensor] = None
 
     def reset_warm_start(self) -> None:
         """Forget the previous pair: the next call runs cold."""
@@ -203,6 +218,7 @@ class FlowInference:
         with torch.cuda.device(self.device):
             frames = self._pin_in.to(self.device, non_blocking=True)
             self._pin_in_free.record()
+        self._frames_u8 = frames
         images, _ = ingest_frames(frames) if self.scale == 1 else ingest_frames_scaled(frames, self.scale)
         return images[0:1], images[1:2]
 
@@ -214,6 +230,7 @@ class FlowInference:
         if self.scale > 1:  # a plain uint8 upload, then the downscale where the model runs
             frames = torch.stack([torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)),
                                   torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8))]).to(self.device)
+            self._frames_u8 = frames
             images, _ = ingest_frames_scaled(frames, self.scale)
             return images[0:1], images[1:2]
         image1 = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)).permute(2, 0, 1).float()[None]
@@ -336,6 +353,7 @@ class FlowInference:
         if not self.track:
             raise RuntimeError("tracks needs FlowInference(track=True)")
         h, w = prev.shape[:2]
+        self._frames_u8 = None
         image1, image2 = self._padded_pair(prev, curr)
         shape = tuple(image1.shape)
         if self.scale > 1:
@@ -350,12 +368,33 @@ class FlowInference:
             roi = (pad[0], pad[2], w, h)  # the unpadded image inside the padded frame
         fw = flow_up[0:1].float().contiguous()
         bw = flow_up[1:2].float().contiguous() if self.consistency else None
-        pos, prv, ids, age, _, status, _, _ = self._tracker.update(fw, bw, continuous=continuous, roi=roi)
+        seeds = {}
+        if self.track_seeds == "corners":
+            frames = self._frames_u8
+            if frames is None:  # the pair went up as fp32: one more upload, as uint8
+                frames = torch.stack([torch.from_numpy(np.ascontiguousarray(prev, dtype=np.uint8)),
+                                      torch.from_numpy(np.ascontiguousarray(curr, dtype=np.uint8))]).to(self.device)
+            self._frames_u8 = None
+            # image 0 serves a (re)seeded grid, whose points start in the first frame; image 1 the
+            # points born in this step, which live in the second
+            corners, cell_score = corner_seeds(frames, self.track_cell, (w, h), roi[:2],
+                                               min_score=self.track_min_score)
+            seeds = dict(first_seeds=corners[0:1], seeds=corners[1:2])
+        resets = self._tracker.resets
+        pos, prv, ids, age, _, status, _, _ = self._tracker.update(fw, bw, continuous=continuous, roi=roi, **seeds)
         self._track_stamp, self._track_shape = curr_stamp, shape
         if self._track_shift is None or self._track_shift[0] != (roi, fw.device):
             self._track_shift = ((roi, fw.device), torch.tensor([roi[0], roi[1]], dtype=torch.float32).to(fw.device))
         shift = self._track_shift[1]
         arrays = dict(points=(pos - shift)[0], prev=(prv - shift)[0], ids=ids[0], age=age[0], status=status[0])
+        if seeds:
+            kept = None
+            if self._tracker.resets == resets:  # the pair continued: the survivors keep their score
+                kept = self._track_score
+            else:  # a fresh grid: slot j was born on the first frame's seed of cell j
+                kept = cell_score[0:1]
+            self._track_score = slot_scores(pos, age, kept, cell_score[1:2], roi, self.track_cell)
+            arrays["score"] = self._track_score[0]
         return flow_up, arrays
 
     def _to_pinned(self, name: str, t: torch.Tensor) -> torch.Tensor:
@@ -374,7 +413,8 @@ class FlowInference:
         ``prev`` (N, 2) where each was in the previous frame (NaN for a new point), ``ids`` (N,)
         int64, ``age`` (N,) int32 and ``status`` (N,) uint8, the fate of the point the slot held
         before: 0 tracked (the only slots whose ``prev`` is a correspondence), 1 inconsistent, 2 left
-        the image, 3 crowded out.  With ``consistency`` the model runs on the pair and the swapped
+        the image, 3 crowded out.  With ``track_seeds="corners"`` a sixth array ``score`` (N,) int32:
+        the corner score the slot's point was born with (-1: a cell without candidates).  With ``consistency`` the model runs on the pair and the swapped
         pair and the forward-backward check applies; otherwise only the frame test.  With
         ``device_io`` the arrays come back through pinned buffers under one synchronisation."""
         with torch.inference_mode():
@@ -438,6 +478,8 @@ class RaftRosNode:
         self._pub_occ = rospy.Publisher("/raft_occlusion", image_msg, queue_size=100) if self.occlusion else None
         self.track = bool(_get_param(rospy, "/RAFT/track", False))
         self.track_cell = int(_get_param(rospy, "/RAFT/track_cell", 32))
+        self.track_seeds = str(_get_param(rospy, "/RAFT/track_seeds", "grid"))
+        self.track_min_score = int(_get_param(rospy, "/RAFT/track_min_score", 0))
         self.scale = int(_get_param(rospy, "/RAFT/scale", 1))
         self._pub_tracks = None
         if self.track:
@@ -459,7 +501,9 @@ class RaftRosNode:
                                       device_io=bool(_get_param(rospy, "/RAFT/device_io", False)),
                                       consistency=self.occlusion,
                                       **(dict(scale=self.scale) if self.scale != 1 else {}),
-                                      **(dict(track=True, track_cell=self.track_cell) if self.track else {}))
+                                      **(dict(track=True, track_cell=self.track_cell) if self.track else {}),
+                                      **(dict(track_seeds=self.track_seeds, track_min_score=self.track_min_score)
+                                         if self.track and self.track_seeds != "grid" else {}))
             print("Initialize RAFT finish!")
         self.inference = inference
         self._thread: Optional[threading.Thread] = None
@@ -497,7 +541,8 @@ class RaftRosNode:
     def tracks_msg(self, tracks, header):
         """The tracked points (status 0) as a sensor_msgs/PointCloud: ``points[i] = (x, y, 0)`` in
         the current frame, channels ``id`` (``id mod 2^24``: exact in float32), ``prev_x``,
-        ``prev_y`` (the same point in the previous frame) and ``age`` (pairs survived)."""
+        ``prev_y`` (the same point in the previous frame) and ``age`` (pairs survived); with corner
+        seeds also ``score``, the corner score the point was born with."""
         cloud_cls, point_cls, channel_cls = self._track_msgs
         keep = tracks["status"] == 0
         pts, prv = tracks["points"][keep], tracks["prev"][keep]
@@ -506,6 +551,8 @@ class RaftRosNode:
         msg.points = [point_cls(x=float(x), y=float(y), z=0.0) for x, y in pts]
         values = (("id", tracks["ids"][keep] % (1 << 24)), ("prev_x", prv[:, 0]), ("prev_y", prv[:, 1]),
                   ("age", tracks["age"][keep]))
+        if "score" in tracks:
+            values += (("score", tracks["score"][keep]),)
         msg.channels = [channel_cls(name=name, values=np.asarray(v, dtype=np.float32).tolist()) for name, v in values]
         return msg
 
